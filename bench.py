@@ -1,6 +1,13 @@
 """bench.py — device-resident delta signature + rolling match on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  --full adds what
+the headline does not need: `cpu_baseline`, `host_inclusive` and (c3) the C4 and C5 legs
+(null / absent in a plain run).  --dump-outputs DIR writes what the last timed step returned
+to its caller (op list, signature, hashes, output bytes, statistics) as DIR/<name>.npy in
+float64; arrays of more than 2^20 values are sampled at fixed, seeded positions.  The inputs
+are generated from fixed seeds, so the same arguments give the same outputs.
 
 One *step* = one pass of sy's delta hot path over one batch of synthetic input
 already resident in HBM:
@@ -43,8 +50,8 @@ max-over-ranks time.
 
 The JSON line carries `roofline` for the dominant kernel (per-launch HIP-event
 time measured inside the timed region, algorithmic bytes per launch, HBM peak
-8 TB/s) and `cpu_baseline` (the oracle restatement of sy's CPU path, timed on a
-bounded sample on this host; rank 0 at N=1 only).
+8 TB/s) and, with --full, `cpu_baseline` (the oracle restatement of sy's CPU path, timed
+on a bounded sample on this host; rank 0 at N=1 only).
 """
 from __future__ import annotations
 
@@ -100,15 +107,22 @@ def parse():
                          "calls signature_batch + index_create_batch + match_batch")
     ap.add_argument("--device-walk", action="store_true",
                     help="resolve the greedy walks on the device (K5b, SYDELTA_DEVICE_WALK=1; c4/c5/path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-inclusive", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the CPU baseline, the "
+                         "host-inclusive rate and (c3) the C4 and C5 legs; without it those fields are null / absent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-host-inclusive", action="store_true", help="--full: skip the host-inclusive rate")
     ap.add_argument("--no-legs", action="store_true",
-                    help="c3: skip the C4 and C5 legs that follow the headline (their objects in the line)")
+                    help="--full, c3: skip the C4 and C5 legs that follow the headline (their objects in the line)")
     ap.add_argument("--proxy-world", type=int, default=0,
                     help="c5 on one GPU: time rank --proxy-rank of a W-rank job (the other ranks' signatures "
                          "precomputed and concatenated in place of the all-gather; index over all W chunks' keys)")
     ap.add_argument("--proxy-rank", type=int, default=0)
     a = ap.parse_args()
+    if not a.full:  # a plain run: set up, warm up, time the steps, print the line
+        a.no_cpu_baseline = a.no_host_inclusive = a.no_legs = True
     if a.device_walk:
         os.environ["SYDELTA_DEVICE_WALK"] = "1"
     if a.size_gib is None:
@@ -724,6 +738,51 @@ def time_steps(step, steps: int, warmup: int, world: int):
     return el, last
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per file: 8 MiB of float64; a run writes at most five files
+
+
+def dump_array(x, wide: bool = False):
+    """`x` (a numpy array or a torch tensor of integers or floats, flattened) as a float64 numpy
+    array; a tensor's integers are read as unsigned.  `wide`: 8-byte elements whose values may exceed 2^53 (hashes) become rows of their
+    (low, high) 32-bit words, so float64 holds them exactly.  An array of more than
+    DUMP_MAX_ELEMS values is sampled at a fixed, seeded, sorted set of its rows (the same set
+    whenever the length is the same)."""
+    import numpy as np
+    import torch
+
+    if isinstance(x, torch.Tensor):
+        x = x.reshape(-1)
+        x = x.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[x.element_size()]
+                   if not x.is_floating_point() else x.dtype)
+        if wide:
+            x = x.view(torch.int32).reshape(-1, 2)
+    else:
+        x = np.ascontiguousarray(x).reshape(-1)
+        if wide:
+            x = x.view(np.uint32).reshape(-1, 2)
+    rows = x.shape[0]
+    keep = DUMP_MAX_ELEMS // (2 if wide else 1)
+    if rows > keep:
+        pick = np.sort(np.random.default_rng(0x5E1DD0).integers(0, rows, keep))
+        x = x[torch.from_numpy(pick).to(x.device)] if isinstance(x, torch.Tensor) else x[pick]
+    if isinstance(x, torch.Tensor):
+        x = x.cpu().numpy()
+        if x.dtype.kind == "i":  # the library's integer tensors carry unsigned values
+            x = x.view(x.dtype.str.replace("i", "u"))
+    return x.astype(np.float64)
+
+
+def dump_outputs(dirname: str, outs: dict, rank: int = 0) -> None:
+    """Write each array of `outs` (name -> array, or (array, wide)) as dirname/<name>.npy
+    (rank r > 0 of a multi-rank run: <name>_rank<r>.npy)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, x in outs.items():
+        x, wide = x if isinstance(x, tuple) else (x, False)
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if rank else "") + ".npy"), dump_array(x, wide))
+
+
 def c4_step(dev, basis, new, files, bs: int, device: int, strm, calls: str = "pairs"):
     """One batch of files = (boff, blen, soff, slen): the signature of every basis and the match
     of every source (K10 walks every file on the device) -- one sydelta_delta_pairs_device call
@@ -1073,6 +1132,8 @@ def main():
         c4_groups = [g for g in c4_groups if g[1] > g[0]]
         c4_pool = ThreadPoolExecutor(len(c4_groups))
 
+    held = {}  # c2 / xxh3: the last step's result arrays (the step returns no object that carries them)
+
     def step():
         if args.workload == "path":
             sig = ctypes.POINTER(_lib.BlockChecksumC)()
@@ -1090,7 +1151,7 @@ def main():
                     lib.sydelta_delta_free(h)
             return {k: getattr(st, k) for k, _ in _lib.MatchStatsC._fields_}
         if args.workload == "c2":
-            dev.signature(basis, bs, stream=stream)
+            held["weak"], held["strong"] = dev.signature(basis, bs, stream=stream)
             return None
         if args.workload in ("c3", "c3b"):
             w, s = dev.signature(basis[:nb_bytes], bs, stream=stream)
@@ -1102,7 +1163,7 @@ def main():
             _, st = dev.apply_device(basis, apply_d, new, out=apply_out, stream=stream)
             return st
         if args.workload == "xxh3":
-            h = dev.xxh3_batch(basis, xxh_offs, xxh_lens, stream=stream)
+            h = held["hashes"] = dev.xxh3_batch(basis, xxh_offs, xxh_lens, stream=stream)
             return {"files": len(h), "hash0": f"{int(h[0]):016x}"}
         if args.workload == "local":
             # the local delta decision (ratio.rs) then the block compare (local.rs)
@@ -1259,6 +1320,32 @@ def main():
                                                (bytes_per_step / (step_ms * 1e-3) / GIB) /
                                                ceil["information_bound"]["value_GiBps"], 4))
     kernels = {k: {"avg_ms": round(v["ms"] / max(1, v["count"]), 4), "launches": v["count"]} for k, v in prof.items()}
+
+    if args.dump_outputs:
+        # what the last timed step handed its caller: the op list (c3 / c3b / c5), the signature
+        # (c2), the hashes (xxh3), the bytes it wrote to its output buffer, and its statistics
+        outs = {}
+        if hasattr(last, "kind"):
+            outs.update(ops_kind=last.kind, ops_a=last.a, ops_b=last.b)
+        if args.workload == "c2":
+            outs.update(weak=held["weak"], strong=(held["strong"], True))
+        elif args.workload == "xxh3":
+            outs["hashes"] = (held["hashes"], True)
+        elif args.workload == "apply":
+            outs["output"] = apply_out[:n]
+        elif args.workload == "local":
+            outs["changed_flags"] = local_flags
+        elif args.workload == "zstd":
+            outs["frame"] = zstd_out[:last["frame_bytes"]]
+        elif args.workload == "json":
+            outs["json"] = json_out[:last["json_bytes"]]
+        elif args.workload == "dparse":
+            outs["literal"] = dp_lit[:last["literal_bytes"]]
+        elif args.workload == "sigjson":
+            outs.update(json=sj_out[:last["json_bytes"]], records=sj_recs)
+        if isinstance(stats, dict):  # numeric fields in the dict's order
+            outs["stats"] = np.array([float(v) for v in stats.values() if isinstance(v, (bool, int, float))])
+        dump_outputs(args.dump_outputs, outs, rank)
 
     legs = None
     if args.workload == "c3" and not args.no_legs:

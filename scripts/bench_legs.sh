@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 cd "$R"
 for w in $LEGS; do
   echo "== $w" >&2
-  timeout -k 10 400 python -u bench.py --workload "$w" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+  timeout -k 10 400 python -u bench.py --full --workload "$w" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
   rc=$?
   if [ $rc -ne 0 ]; then echo "== $w rc=$rc" >&2; tail -20 "$OUT/bench_$w.err"; exit 1; fi
   python - "$OUT/bench_$w.json" "$w" <<'PY'

@@ -16,7 +16,7 @@ step 900 python -u -m pytest tests -m "gpu and firstrun" -x -v --timeout 240 --t
   -p no:cacheprovider > "$OUT/pytest.log" 2>&1 || { tail -40 "$OUT/pytest.log"; exit 1; }
 tail -4 "$OUT/pytest.log"
 for w in sigjson dparse zstd; do
-  step 400 python -u bench.py --workload "$w" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || { tail -20 "$OUT/bench_$w.err"; exit 1; }
+  step 400 python -u bench.py --full --workload "$w" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || { tail -20 "$OUT/bench_$w.err"; exit 1; }
   tail -c 600 "$OUT/bench_$w.json"; echo
 done
 step 400 python -u bench.py --workload c5 --device-walk > "$OUT/bench_c5_dev.json" 2> "$OUT/bench_c5_dev.err" || { tail -20 "$OUT/bench_c5_dev.err"; exit 1; }

@@ -11,7 +11,7 @@ cd "$R"
 step() { local t=$1; shift; echo "== $* (limit ${t}s)" >&2; timeout -k 10 "$t" "$@"; local rc=$?; echo "== rc=$rc" >&2; return $rc; }
 [ -n "${SKIP_TESTS:-}" ] || step 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -p no:cacheprovider > "$OUT/pytest.log" 2>&1 || { tail -30 "$OUT/pytest.log"; exit 1; }
 tail -3 "$OUT/pytest.log" 2>/dev/null
-step 600 python bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { cat "$OUT/bench.err" | tail -20; exit 1; }
+step 600 python bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { cat "$OUT/bench.err" | tail -20; exit 1; }
 cat "$OUT/bench.json"
 cd /tmp
 # profiled runs: the same workload without the CPU baseline and host-inclusive legs,

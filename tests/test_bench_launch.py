@@ -80,7 +80,7 @@ def test_launcher_forwards_rank0_legs(n):
     """The C4 / C5 legs ride on rank 0's line (stub: the legs' objects built by bench.c4_leg /
     c5_leg with fixed timings): forwarded to the launcher's stdout once, aggregated over all
     N ranks (C4: the 10 000 files' bytes per max-rank step; C5: N chunks of 2 x 8 GiB)."""
-    p = run(n, {"SYDELTA_BENCH_STUB_LEGS": "1"}, args=("--steps", "4"))
+    p = run(n, {"SYDELTA_BENCH_STUB_LEGS": "1"}, args=("--full", "--steps", "4"))
     assert p.returncode == 0, p.stderr
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{") and '"c4"' in ln]
     assert len(lines) == 1

@@ -146,3 +146,31 @@ def test_cpu_baselines_other_workloads_small():
     s = torch.from_numpy(np.arange(256, dtype=np.uint64).view(np.int64))
     sj = bench.cpu_sigjson_baseline(w, s, bs)
     assert sj["value"] > 0 and sj["sample"].startswith("host writer + host parser (C calls only), 256 entries")
+
+
+def test_dump_outputs_small(tmp_path):
+    """--dump-outputs: float64 .npy files; 64-bit hashes as exact (low, high) words; a tensor's
+    integers unsigned; an array of more than DUMP_MAX_ELEMS values sampled at the same sorted
+    positions on every call."""
+    import numpy as np
+    import torch
+
+    h = np.array([0xFFFFFFFFFFFFFFFF, 0x0123456789ABCDEF, 5], np.uint64)
+    w = torch.from_numpy(np.array([0xFFFFFFFE, 7], np.uint32).view(np.int32))
+    big = np.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=np.uint64)
+    outs = {"ops_a": np.array([0, 1 << 40], np.uint64), "hashes": (h, True), "strong": (torch.from_numpy(h.view(np.int64)), True),
+            "weak": w, "big": big, "bytes": torch.arange(256, dtype=torch.uint8)}
+    bench.dump_outputs(str(tmp_path / "d"), outs)
+    got = {k: np.load(tmp_path / "d" / f"{k}.npy") for k in outs}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["ops_a"].tolist() == [0.0, float(1 << 40)]
+    for k in ("hashes", "strong"):
+        assert got[k].shape == (3, 2)
+        assert [int(lo) | int(hi) << 32 for lo, hi in got[k]] == [int(v) for v in h]
+    assert got["weak"].tolist() == [float(0xFFFFFFFE), 7.0]
+    assert got["bytes"].tolist() == list(range(256))
+    assert got["big"].shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(got["big"]) >= 0)
+    assert got["big"].max() < big.size and got["big"].max() > big.size // 2
+    assert np.array_equal(got["big"], bench.dump_array(big))
+    bench.dump_outputs(str(tmp_path / "d"), {"weak": w}, rank=2)
+    assert np.array_equal(np.load(tmp_path / "d" / "weak_rank2.npy"), got["weak"])
