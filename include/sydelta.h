@@ -439,6 +439,37 @@ int sydelta_xxh3_batch_device(int device, const uint8_t *d_buf, uint64_t buf_len
                               uint64_t nfiles, void *stream, uint64_t *out);
 
 /* ---------------------------------------------------------------------------
+ * Whole-file BLAKE3-256: the `Cryptographic` arm of IntegrityVerifier::compute_file_checksum
+ * (src/integrity/mod.rs:100-112; sy --verify / --paranoid, checksumdb.rs).  Hashes are the
+ * 32 bytes of blake3::Hash::as_bytes().
+ * ------------------------------------------------------------------------- */
+#define SYDELTA_BLAKE3_LEN 32
+/* Blake3Hasher::hash_data (src/integrity/blake3.rs:32-36) of bytes in device memory:
+ * out = blake3(d_buf[0, len)).  len == 0 returns the constant hash without a device. */
+int sydelta_blake3_device(int device, const uint8_t *d_buf, uint64_t len, void *stream, uint8_t out[32]);
+/* The same for nfiles files [offs[f], offs[f] + lens[f]) of d_buf (host arrays), the verify
+ * loop of integrity/mod.rs:104 over Blake3Hasher::hash_file: out + 32 f (host) = hash of
+ * file f.  Every range must lie inside [0, buf_len). */
+int sydelta_blake3_batch_device(int device, const uint8_t *d_buf, uint64_t buf_len, const uint64_t *offs,
+                                const uint64_t *lens, uint64_t nfiles, void *stream, uint8_t *out /* nfiles*32 */);
+/* A piece of a sharded blake3::Hasher::update stream (blake3.rs:21-27 reads a file in pieces):
+ * the non-root chaining value of d_buf[0, len), len > 0, whose first 1 KiB chunk is chunk
+ * first_chunk of the whole input.  Pieces of one input: every piece but the last holds the
+ * same power of two 2^k of chunks (so its first_chunk is a multiple of 2^k), the last one
+ * between 1 and 2^k chunks.  An input that is a single piece is sydelta_blake3_device's. */
+int sydelta_blake3_subtree_device(int device, const uint8_t *d_buf, uint64_t len, uint64_t first_chunk,
+                                  void *stream, uint8_t out_cv[32]);
+/* blake3::Hasher::finalize (blake3.rs:28) over such pieces, on the host: joins the pieces'
+ * chaining values cvs (npieces*32 bytes, in order; piece_chunks[i] = chunks of piece i) into
+ * the root hash.  Pieces that break the contract above, or npieces < 2: SYDELTA_E_INVAL. */
+int sydelta_blake3_join(const uint8_t *cvs /* npieces*32 */, const uint64_t *piece_chunks, uint64_t npieces,
+                        uint8_t out[32]);
+/* Blake3Hasher::hash_file (src/integrity/blake3.rs:16-29): the file streamed through the
+ * calling thread's device in 64 MiB pieces.  An empty file needs no device; open/read
+ * failures -> SYDELTA_E_IO. */
+int sydelta_blake3_file(const char *path, uint8_t out[32]);
+
+/* ---------------------------------------------------------------------------
  * Measurement support (used by bench.py; not part of the reference API).
  * ------------------------------------------------------------------------- */
 /* When on, the library records a HIP event pair around every kernel it

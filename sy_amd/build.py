@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsydelta.so")
-SOURCES = ["sydelta_kernels.hip", "sydelta_filewalk.hip", "sydelta_api.cpp", "sydelta_wire.cpp", "sydelta_local.cpp", "sydelta_integrity.cpp"]
+SOURCES = ["sydelta_kernels.hip", "sydelta_filewalk.hip", "sydelta_api.cpp", "sydelta_wire.cpp", "sydelta_local.cpp", "sydelta_integrity.cpp",
+           "sydelta_blake3.hip", "sydelta_blake3.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "sydelta.h")]
 # objects stay in build/obj (the host sanitizer test links sydelta_kernels.o)
 OBJDIR = os.path.join(ROOT, "build", "obj")
@@ -38,6 +39,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     t_hdr = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
     for src in SOURCES:
         obj = os.path.join(OBJDIR, src.rsplit(".", 1)[0] + ".o")
+        if obj in objs:  # sydelta_blake3.hip and sydelta_blake3.cpp
+            obj = os.path.join(OBJDIR, src + ".o")
         objs.append(obj)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(t_hdr, os.path.getmtime(
                 os.path.join(CSRC, src))):

@@ -16,6 +16,7 @@ Reference functions and where they are mirrored:
 ``estimate_change_ratio`` ratio.rs:78    ``estimate_change_ratio`` (sampled blocks hashed
                                          on the device)
 ``Adler32``            rolling.rs:16     ``Adler32``
+``Blake3Hasher``       integrity/blake3.rs:12  ``Blake3Hasher`` (hashed on the device)
 ``BlockChecksum``/``Delta``/``DeltaOp``  dataclasses below
 =======================================  =====================================
 """
@@ -115,6 +116,36 @@ class Adler32:
 
     def reset(self) -> None:
         self.a, self.b = 1, 0
+
+
+class Blake3Hasher:
+    """integrity/blake3.rs:12-37: the `Cryptographic` checksum of integrity/mod.rs:100-112,
+    as the 32 bytes of ``blake3::Hash::as_bytes()``."""
+
+    @staticmethod
+    def hash_file(path) -> bytes:
+        """blake3.rs:16-29: the file streamed through the calling thread's device."""
+        out = (ctypes.c_uint8 * 32)()
+        check(lib.sydelta_blake3_file(_pathb(path), out))
+        return bytes(out)
+
+    @staticmethod
+    def hash_data(data: bytes, device: int = -1) -> bytes:
+        """blake3.rs:32-36 of an in-memory image (uploaded, then hashed on the device)."""
+        out = (ctypes.c_uint8 * 32)()
+        if not data:
+            check(lib.sydelta_blake3_device(device, None, 0, None, out))
+            return bytes(out)
+        if device < 0:
+            d = ctypes.c_int(0)
+            check(lib.sydelta_thread_device(ctypes.byref(d)))  # SYDELTA_E_NODEV without a GPU
+            device = d.value
+        import torch
+
+        buf = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(f"cuda:{device}")
+        check(lib.sydelta_blake3_device(device, buf.data_ptr(), buf.numel(),
+                                        int(torch.cuda.current_stream(device).cuda_stream), out))
+        return bytes(out)
 
 
 def calculate_block_size(file_size: int) -> int:

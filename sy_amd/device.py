@@ -400,6 +400,37 @@ def xxh3_batch(buf: torch.Tensor, offs, lens, stream=None) -> np.ndarray:
     return out
 
 
+def blake3(buf: torch.Tensor, stream=None) -> bytes:
+    """Blake3Hasher::hash_data (integrity/blake3.rs:32-36) of device bytes: the 32-byte BLAKE3 hash."""
+    out = (ctypes.c_uint8 * 32)()
+    n = buf.numel()
+    check(lib.sydelta_blake3_device(buf.device.index or 0, _ptr(buf) if n else None, n, _stream(stream), out))
+    return bytes(out)
+
+
+def blake3_batch(buf: torch.Tensor, offs, lens, stream=None) -> np.ndarray:
+    """BLAKE3 of files [offs[f], offs[f] + lens[f]) of `buf`: uint8 (n, 32)."""
+    o = np.ascontiguousarray(offs, dtype=np.uint64)
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    if o.shape != ln.shape:
+        raise ValueError("offs and lens differ in length")
+    if len(ln) and int((o + ln).max()) > buf.numel():
+        raise ValueError("file range outside the buffer")
+    out = np.zeros((len(ln), 32), dtype=np.uint8)
+    check(lib.sydelta_blake3_batch_device(buf.device.index or 0, _ptr(buf), buf.numel(), o.ctypes.data, ln.ctypes.data,
+                                          len(ln), _stream(stream), out.ctypes.data))
+    return out
+
+
+def blake3_subtree(buf: torch.Tensor, first_chunk: int, stream=None) -> bytes:
+    """Chaining value of a piece of a larger input whose first 1 KiB chunk is chunk `first_chunk`
+    of that input (the piece contract: include/sydelta.h); joined by shard.blake3_join."""
+    out = (ctypes.c_uint8 * 32)()
+    check(lib.sydelta_blake3_subtree_device(buf.device.index or 0, _ptr(buf), buf.numel(), first_chunk,
+                                            _stream(stream), out))
+    return bytes(out)
+
+
 def synth_fill(buf: torch.Tensor, seed: int, stream=None) -> None:
     check(lib.sydelta_synth_fill(_ptr(buf), buf.numel(), seed & 0xFFFFFFFFFFFFFFFF, _stream(stream)))
 

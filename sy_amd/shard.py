@@ -11,6 +11,8 @@
   (block-aligned copies, the usual case); otherwise the walks from the first
   mismatch on are redone in rank order, one broadcast per hop.  The chained op
   lists joined in rank order equal the single-device result.
+* The BLAKE3 hash of one large file shards the same way with one all-gather
+  (`blake3_join`): each rank hashes its aligned share into a 32-byte chaining value.
 """
 from __future__ import annotations
 
@@ -65,6 +67,35 @@ def walk_chain(chunk, rank: int, world: int, pos_begin: int, gather, bcast):
                 delta, ex = chunk.walk(e)
         e = bcast(ex if rank == g else 0, g)
     return delta, mine
+
+
+def blake3_join(cvs, piece_chunks) -> bytes:
+    """Root BLAKE3 hash of an input from the chaining values of its pieces, in order
+    (sydelta_blake3_join).  `cvs`: the 32-byte values of `device.blake3_subtree`;
+    `piece_chunks[i]`: 1 KiB chunks of piece i.  Every piece but the last holds the same
+    power of two of chunks, the last between 1 and that many (anything else, or fewer than
+    two pieces, raises SyDeltaError).
+
+    One file sharded over ranks, each holding the contiguous share
+    [rank * share, rank * share + n) with share = 1024 * 2^k bytes::
+
+        cv = device.blake3_subtree(my_bytes, first_chunk=rank * share // 1024)
+        t = torch.frombuffer(bytearray(cv), dtype=torch.uint8).to(dev)
+        out = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(out, t)
+        digest = blake3_join([bytes(o.cpu().numpy()) for o in out], chunks_per_rank)
+    """
+    import ctypes
+
+    from ._lib import check, lib
+
+    cvs = [bytes(c) for c in cvs]
+    if any(len(c) != 32 for c in cvs) or len(cvs) != len(piece_chunks):
+        raise ValueError("one 32-byte chaining value per piece")
+    pc = (ctypes.c_uint64 * max(1, len(cvs)))(*[int(c) for c in piece_chunks])
+    out = (ctypes.c_uint8 * 32)()
+    check(lib.sydelta_blake3_join(b"".join(cvs) or None, pc, len(cvs), out))
+    return bytes(out)
 
 
 def torch_collectives(dist, device):
