@@ -39,6 +39,9 @@ sy_amd._lib = mod
 import sy_amd.delta as D  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import adler_twins as T  # noqa: E402
+
 C = O.C()
 
 
@@ -646,7 +649,8 @@ def _ops(lib, h):
 def batch_and_chunk_checks():
     """The device-pointer entry points on host memory: batched signature + index + match
     (the C4 path, threaded walks at >= 64 files) and a file matched in 1/2/3/8 chained
-    chunks (the C5 path), each against the oracle."""
+    chunks (the C5 path), each against the oracle.  The weak-collision scenarios of
+    tests/adler_twins.py ride in every batch and go through the chunk loop too."""
     import ctypes
 
     from sy_amd._lib import check, lib
@@ -682,6 +686,12 @@ def batch_and_chunk_checks():
                         s2[q] ^= 0x11
                 bases.append(b)
                 srcs.append(s2)
+            # the weak-collision scenarios (synthetic-R6: its signature entries put in below)
+            twins = T.scenarios(bs, seed=3)
+            for sc in twins:
+                bases.append(np.frombuffer(sc.basis, np.uint8))
+                srcs.append(np.frombuffer(sc.src, np.uint8))
+            nf = len(bases)
 
             def pack(parts):
                 offs, cur = [], 0
@@ -701,6 +711,14 @@ def batch_and_chunk_checks():
             st = np.zeros(max(tot, 1), np.uint64)
             check(lib.sydelta_signature_batch_device(0, vp(bbuf), vp(boff), vp(blen), nf, bs, vp(w), vp(st), None))
             fb = np.concatenate([[0], np.cumsum(nblk)]).astype(np.int64)
+            sigs = {}  # file -> (weak, strong, size) where they are not the basis's own
+            for k, sc in enumerate(twins, nf - len(twins)):
+                if sc.sig is not None:
+                    ew, es, ez = C.compute_checksums(bases[k], bs)
+                    assert np.array_equal(w[fb[k]:fb[k + 1]], ew) and np.array_equal(st[fb[k]:fb[k + 1]], es), (bs, k)
+                    assert np.array_equal(ez, sc.sig[2])
+                    w[fb[k]:fb[k + 1]], st[fb[k]:fb[k + 1]] = sc.sig[0], sc.sig[1]
+                    sigs[k] = sc.sig
             last = np.where(nblk > 0, blen - (nblk - 1) * bs, 0).astype(np.uint64)
             ix = ctypes.c_void_p()
             check(lib.sydelta_index_create_batch(0, vp(w), vp(st), vp(nblk.astype(np.uint64)), vp(last), nf, bs, 1,
@@ -711,9 +729,11 @@ def batch_and_chunk_checks():
             check(lib.sydelta_match_batch_device(ix, vp(sbuf), vp(soff), vp(slen), nf, None, ctypes.byref(bt)))
             assert (lib.emu_expand_files() > ex0) == probe.endswith("dx"), (bs, probe)  # the expansion's path
             for k in range(nf):
-                ew, es, ez = C.compute_checksums(bases[k], bs)
+                ew, es, ez = sigs[k] if k in sigs else C.compute_checksums(bases[k], bs)
                 assert np.array_equal(w[fb[k]:fb[k + 1]], ew) and np.array_equal(st[fb[k]:fb[k + 1]], es), (bs, k)
                 exp = O.ops_from_arrays(*C.generate_delta(srcs[k], ew, es, ez, bs))
+                if k >= nf - len(twins):
+                    assert exp == twins[k - (nf - len(twins))].expect, (bs, k)
                 got = _ops(lib, lib.sydelta_delta_batch_get(bt, k))
                 assert got == exp, ("batch", bs, probe, k)
                 n_checks += 1
@@ -737,12 +757,11 @@ def batch_and_chunk_checks():
     os.environ.pop("SYDELTA_FILE_SEGS", None)
     os.environ.pop("SYDELTA_DEVICE_EXPAND", None)
     # chunked: one file in 1/2/3/8 chunks, walks chained in order, parts appended
-    for bs in (512, 4096):
-        basis = O.synth_bytes(300 * bs + 77, 0x700)
-        s2 = np.concatenate([basis[:10 * bs], np.frombuffer(b"Q", np.uint8), basis[10 * bs:150 * bs],
-                             basis[200 * bs:]])
-        for q in rng.integers(0, s2.size, 20):
-            s2[q] ^= 0x22
+    lib.emu_chunk_units.restype = ctypes.c_uint64
+
+    def chunked(bs, basis, s2, sig, tag):
+        """s2 against basis (sig: its (weak, strong, size) where not the basis's own) in 1/2/3/8 chunks."""
+        n_done = 0
         L = s2.size
         sb = np.zeros(L + 32, np.uint8)
         sb[:L] = s2
@@ -752,15 +771,19 @@ def batch_and_chunk_checks():
         bb = np.zeros(basis.size + 16, np.uint8)
         bb[:basis.size] = basis
         check(lib.sydelta_signature_device(0, vp(bb), basis.size, bs, vp(w), vp(st), None))
-        ix = ctypes.c_void_p()
-        check(lib.sydelta_index_create(0, vp(w), vp(st), nb, bs, basis.size - (nb - 1) * bs, 1, None,
-                                       ctypes.byref(ix)))
         ew, es, ez = C.compute_checksums(basis, bs)
+        assert np.array_equal(w, ew) and np.array_equal(st, es), tag
+        if sig is not None:
+            ew, es, ez = sig
+            w[:], st[:] = ew, es
+        ix = ctypes.c_void_p()
+        check(lib.sydelta_index_create(0, vp(w), vp(st), nb, bs, int(ez[-1]), 1, None, ctypes.byref(ix)))
         exp = O.ops_from_arrays(*C.generate_delta(s2, ew, es, ez, bs))
         npos = L - bs + 1
         nbp = -(-npos // bs)
-        lib.emu_chunk_units.restype = ctypes.c_uint64
         for nch in (1, 2, 3, 8):
+            if nch > nbp:  # (a scenario's few blocks)
+                continue
             # 1p: the device walk's launches in one sub-range per segment; ...dx: the ops written
             # by the emulated k_chunk_write (SYDELTA_DEVICE_EXPAND=1); 1pa: the default with this
             # host's threads (> 4): the last part's ops written by it, the others' on the host
@@ -789,12 +812,28 @@ def batch_and_chunk_checks():
                     lib.sydelta_delta_free(d)
                     lib.sydelta_chunk_free(ch)
                     entry = ex.value
-                assert _ops(lib, acc) == exp, ("chunks", bs, nch, probe)
+                assert _ops(lib, acc) == exp, ("chunks", tag, bs, nch, probe)
                 if probe not in ("0", "1pa"):  # the path the ops took (1pa: as the re-walks leave it)
-                    assert (lib.emu_chunk_units() > cu0) == probe.endswith("dx"), ("chunk writes", bs, nch, probe)
+                    assert (lib.emu_chunk_units() > cu0) == probe.endswith("dx"), ("chunk writes", tag, bs, nch, probe)
                 lib.sydelta_delta_free(acc)
-                n_checks += 1
+                n_done += 1
         lib.sydelta_index_free(ix)
+        return exp, n_done
+
+    for bs in (512, 4096):
+        basis = O.synth_bytes(300 * bs + 77, 0x700)
+        s2 = np.concatenate([basis[:10 * bs], np.frombuffer(b"Q", np.uint8), basis[10 * bs:150 * bs],
+                             basis[200 * bs:]])
+        for q in rng.integers(0, s2.size, 20):
+            s2[q] ^= 0x22
+        n_checks += chunked(bs, basis, s2, None, "edits")[1]
+    # the weak-collision scenarios, each a file of its own (the candidate lists of the index's
+    # tables, the walk's resumption one byte after a weak hit that fails verification)
+    for bs in (512, 4096):
+        for sc in T.scenarios(bs, seed=4):
+            exp, k = chunked(bs, np.frombuffer(sc.basis, np.uint8), np.frombuffer(sc.src, np.uint8), sc.sig, sc.name)
+            assert exp == sc.expect and k, (bs, sc.name)
+            n_checks += k
     os.environ.pop("SYDELTA_PROBE", None)
     os.environ.pop("SYDELTA_CHUNK_PIPE", None)
     os.environ.pop("SYDELTA_DEVICE_EXPAND", None)

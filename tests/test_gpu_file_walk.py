@@ -34,9 +34,10 @@ def _pack(parts):
     return buf, np.array(offs, np.uint64), np.array([len(p) for p in parts], np.uint64)
 
 
-def _batch(gpu, pairs, bs, walk, monkeypatch, dx=""):
+def _batch(gpu, pairs, bs, walk, monkeypatch, dx="", sigs=None):
     """Batched signature + index + match of (src, basis) pairs; walk: SYDELTA_FILE_WALK; dx:
-    SYDELTA_DEVICE_EXPAND (the op lists expanded by k_walk_expand or on the host)."""
+    SYDELTA_DEVICE_EXPAND (the op lists expanded by k_walk_expand or on the host); sigs: {file:
+    (weak, strong)} put in place of that basis's own signature entries (as many)."""
     monkeypatch.setenv("SYDELTA_FILE_WALK", walk)
     monkeypatch.setenv("SYDELTA_DEVICE_EXPAND", dx)
     bbuf, boff, blen = _pack([b for _, b in pairs])
@@ -44,6 +45,11 @@ def _batch(gpu, pairs, bs, walk, monkeypatch, dx=""):
     w, s = gpu.signature_batch(bbuf, boff, blen, bs)
     nblk = [-(-int(x) // bs) for x in blen]
     last = [int(x) - (k - 1) * bs if k else 0 for x, k in zip(blen, nblk)]
+    for f, (fw, fs) in (sigs or {}).items():
+        o = sum(nblk[:f])
+        assert len(fw) == len(fs) == nblk[f]
+        w[o:o + nblk[f]] = _sig_tensor(fw, np.uint32, np.int32)
+        s[o:o + nblk[f]] = _sig_tensor(fs, np.uint64, np.int64)
     idx = gpu.BatchIndex(w, s, nblk, last, bs)
     gpu.set_profiling(True)
     gpu.profile(reset=True)
@@ -52,6 +58,12 @@ def _batch(gpu, pairs, bs, walk, monkeypatch, dx=""):
     gpu.set_profiling(False)
     idx.close()
     return out, tot, prof
+
+
+def _sig_tensor(values, utype, itype):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(values, dtype=utype).view(itype).copy()).cuda()
 
 
 def _expanded():
@@ -214,12 +226,16 @@ def _to_dev(data: bytes, pad: int = 16):
     return t
 
 
-def _chunk_walk(gpu, src: bytes, basis: bytes, bs: int, bounds):
+def _chunk_walk(gpu, src: bytes, basis: bytes, bs: int, bounds, sig=None):
     """Signature + index of basis, then the chunks [bounds[g], bounds[g+1]) of src
-    classified and walked in order (each from the previous one's exit), joined."""
+    classified and walked in order (each from the previous one's exit), joined.  sig: (weak,
+    strong) put in place of the basis's own signature (as many entries)."""
     b = _to_dev(basis)
     w, s = gpu.signature(b[:len(basis)], bs)
     nb = w.numel()
+    if sig is not None:
+        assert len(sig[0]) == len(sig[1]) == nb
+        w, s = _sig_tensor(sig[0], np.uint32, np.int32), _sig_tensor(sig[1], np.uint64, np.int64)
     idx = gpu.Index(w, s, bs, (len(basis) - (nb - 1) * bs) if nb else 0)
     L = len(src)
     parts, entry, chunks = [], 0, []
