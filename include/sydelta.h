@@ -386,6 +386,19 @@ int sydelta_delta_from_json_device(const uint8_t *d_text, uint64_t len, uint8_t 
 uint64_t sydelta_zstd_bound(uint64_t len);
 int sydelta_zstd_compress_device(int device, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t out_cap,
                                  uint64_t *out_len, void *stream);
+/* The inverse, for any writer's frames (sy-remote.rs:160-166: compress::decompress of a
+ * payload that starts with the zstd magic): d_in[0, len) holds exactly one zstd frame
+ * (RFC 8878: Raw / RLE / Compressed blocks, Huffman literals in 1 or 4 streams with direct
+ * or FSE-compressed weights, Treeless literals, Predefined / RLE / FSE / Repeat sequence
+ * tables, matches reaching into earlier blocks).  *out_len = the regenerated size, computed
+ * on the device; the bytes are written when d_out != NULL and out_cap >= *out_len, else
+ * nothing is written and the call still returns SYDELTA_OK (size query).  Any alignment;
+ * nothing outside the two ranges is touched.  SYDELTA_E_INVAL (sydelta_last_error names the
+ * block and the reason; decode such a payload on the host): bad magic, truncated frame,
+ * trailing bytes or a second frame, the reserved header bit, a non-zero Dictionary_ID, the
+ * Content_Checksum flag, 4 GiB or more of output, corrupt content. */
+int sydelta_zstd_decompress_device(int device, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t out_cap,
+                                   uint64_t *out_len, void *stream);
 /* serde_json::from_str::<Delta> (sy-remote.rs:175): a host delta holding its literal
  * bytes, ready for sydelta_apply_delta. */
 int sydelta_delta_from_json(const char *json, uint64_t len, sydelta_delta **out);

@@ -119,6 +119,7 @@ SIGNATURES = [
     ("sydelta_delta_from_json_device", _i, [_vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _pp, _vp]),
     ("sydelta_zstd_bound", _u64, [_u64]),
     ("sydelta_zstd_compress_device", _i, [_i, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
+    ("sydelta_zstd_decompress_device", _i, [_i, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
     ("sydelta_block_compare_device", _i, [_i, _vp, _u64, _vp, _u64, _u64, _vp, _vp, ctypes.POINTER(BlockCompareStatsC)]),
     ("sydelta_estimate_change_ratio_device", _i, [_i, _vp, _u64, _vp, _u64, _u64, ctypes.c_int64, ctypes.c_double,
                                                   _vp, ctypes.POINTER(ChangeRatioC)]),
@@ -159,12 +160,13 @@ def _load() -> ctypes.CDLL:
     for name, res, args in SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
-            # libsydelta.so must export every symbol.  The BLAKE3 entry points live in a
-            # translation unit of their own (sydelta_blake3.cpp); a library built from the
+            # libsydelta.so must export every symbol.  The BLAKE3 entry points and the zstd
+            # decoder live in translation units of their own (sydelta_blake3.cpp,
+            # sydelta_unzstd_api.cpp); a library built from the
             # other host units alone (the emulated-device build of the host-logic tests, loaded
             # through this table from another path) has none of them, and calling one there
             # raises AttributeError.
-            if name.startswith("sydelta_blake3_") and LIB_PATH != os.path.join(HERE, "libsydelta.so"):
+            if name.startswith(("sydelta_blake3_", "sydelta_zstd_decompress_")) and LIB_PATH != os.path.join(HERE, "libsydelta.so"):
                 continue
             raise ImportError(f"{LIB_PATH} does not export {name}")
         fn.restype = res

@@ -354,6 +354,26 @@ def apply_device(basis: torch.Tensor, delta: DeviceDelta, lit: torch.Tensor, out
     return out[:st.bytes_written], {f: int(getattr(st, f)) for f, _ in _lib.DeltaStatsC._fields_}
 
 
+ZSTD_MAGIC = bytes([0x28, 0xB5, 0x2F, 0xFD])
+
+
+def apply_wire(basis: torch.Tensor, payload: torch.Tensor, stream=None):
+    """sy-remote apply-delta (sy-remote.rs:153-179) on a payload in HBM: the zstd magic
+    sniffed, the frame decompressed (or the payload taken as the JSON text), the Delta
+    parsed and applied to `basis`, all on the device.  Returns (rebuilt tensor, stats)."""
+    from . import wire
+
+    text = payload
+    if payload.numel() >= 4 and bytes(payload[:4].cpu().numpy()) == ZSTD_MAGIC:
+        text = wire.zstd_decompress_device(payload, stream=stream)
+    ops, lit, source_size, block_size = wire.delta_from_json_device(text, stream=stream)
+    kind = np.array([o[0] for o in ops], dtype=np.uint32)
+    a = np.array([o[1] for o in ops], dtype=np.uint64)
+    b = np.array([o[2] for o in ops], dtype=np.uint64)
+    delta = DeviceDelta(kind, a, b, source_size, block_size, {})
+    return apply_device(basis, delta, lit, stream=stream)
+
+
 def block_compare(src: torch.Tensor, dst: torch.Tensor, block_size: int, stream=None):
     """The local transport's block-compare loop (local.rs:541-619) on device bytes.
     Returns (changed uint8 tensor with one flag per source block, stats dict with

@@ -174,6 +174,36 @@ def zstd_compress_device(d_text, stream=None, device: int | None = None):
     return out[:got.value]
 
 
+def zstd_decompress_device(d_frame, stream=None, device: int | None = None, out=None):
+    """The bytes of one zstd frame held in a uint8 device tensor, decoded on the device
+    (sy-remote.rs:160-166: compress::decompress), as a uint8 device tensor: frames of any
+    zstd writer (libzstd at any level, streaming or one-shot, and zstd_compress_device's).
+    One size query, then the decode into a tensor of that size: the stages up to the size
+    (scan, tables, entropy decode, stitch) run twice, so a caller that knows a bound passes
+    `out` (a uint8 device tensor) for a single call, the result a view of it; the measured
+    rates are of that form.  Raises SyDeltaError (SYDELTA_E_INVAL)
+    for what the device decoder refuses (a checksummed frame, a dictionary, a second frame,
+    corrupt content, an `out` too small): decode that on the host."""
+    import torch
+
+    from .device import _ptr, _stream
+
+    if device is None:
+        device = d_frame.device.index or 0
+    n = ctypes.c_uint64()
+    fp = _ptr(d_frame) if d_frame.numel() else None
+    if out is None:
+        check(lib.sydelta_zstd_decompress_device(device, fp, d_frame.numel(), None, 0, ctypes.byref(n),
+                                                 _stream(stream)))
+        out = torch.empty(max(1, n.value), dtype=torch.uint8, device=d_frame.device)
+    cap = out.numel()
+    check(lib.sydelta_zstd_decompress_device(device, fp, d_frame.numel(), _ptr(out), cap, ctypes.byref(n),
+                                             _stream(stream)))
+    if n.value > cap:
+        raise _lib.SyDeltaError(_lib.SYDELTA_E_INVAL, f"zstd frame regenerates {n.value} bytes, out holds {cap}")
+    return out[:n.value]
+
+
 def delta_from_json(text: bytes):
     """-> (ops as [("C", offset, size) | ("D", literal bytes)], source_size, block_size)."""
     h = ctypes.c_void_p()
