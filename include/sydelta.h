@@ -268,6 +268,56 @@ const sydelta_delta *sydelta_delta_batch_get(const sydelta_delta_batch *b, uint6
 /* Totals over the batch (weak_hits is only counted per batch). */
 int sydelta_delta_batch_stats(const sydelta_delta_batch *b, sydelta_match_stats *out);
 void sydelta_delta_batch_free(sydelta_delta_batch *b);
+/* The nfiles borrowed delta pointers of a batch, written to out[0..cap) in one call
+ * (returns the count; pointers valid until sydelta_delta_batch_free). */
+uint64_t sydelta_delta_batch_ptrs(const sydelta_delta_batch *b, const sydelta_delta **out, uint64_t cap);
+
+/* applier.rs:22-56 for nfiles independent (basis, delta) pairs in one call.
+ * File f: Copy ops read  d_basis[basis_off[f] + offset, +size), offset+size <= basis_len[f];
+ *         Data ops read  d_lit  [lit_off[f]   + op.a,   +op.b), op.a+op.b   <= lit_len[f];
+ *         output goes to d_out  [out_off[f], +bytes_written[f]), bytes_written[f] <= out_cap[f].
+ *  - Inputs: every offset and length table is a host array of nfiles entries.  deltas[f]
+ *    may come from sydelta_delta_batch_get / sydelta_delta_batch_ptrs, sydelta_delta_from_ops
+ *    or sydelta_match_device; the same pointer may appear more than once.  The Data ops of a
+ *    delta from sydelta_match_batch_device or sydelta_delta_pairs_device index file f's
+ *    source, so lit_off = src_off and lit_len = src_len rebuild the sources.
+ *  - Alignment and size: any byte alignment of every pointer and offset; offsets and arena
+ *    sizes are full 64-bit.
+ *  - Reading: nothing outside file f's basis and literal ranges, beyond the 16-byte granules
+ *    holding their first and last byte (Conventions, "Data layout in HBM").
+ *  - Writing: nothing outside [out_off[f], out_off[f] + bytes_written[f]).  Outputs may be
+ *    packed back to back at odd lengths: two files' outputs may share a 16-byte granule, and
+ *    the partial granules at the ends of an output are written byte by byte.
+ *  - Overlap: the output ranges must be pairwise disjoint, and disjoint from the basis and
+ *    literal arenas.  This is the caller's contract and is not checked; there is no in-place
+ *    apply.
+ *  - Validation: every table entry and every op of every file is validated, overflow-checked,
+ *    before one output byte of any file is written; on any error no output is touched and
+ *    the message names the file and the op ("file F: op I: ...").  Codes as for the
+ *    single-file call: a Copy past the end of file f's basis SYDELTA_E_IO ("past the end of
+ *    the basis"); a Data op outside file f's literal range, an output above out_cap[f], a
+ *    range that leaves its arena (off[f] + len[f] > buf_len), a NULL deltas[f] or a NULL
+ *    table with nfiles > 0: SYDELTA_E_INVAL.
+ *  - nfiles == 0 returns SYDELTA_OK without touching a device.  Files without ops and ops
+ *    with b == 0 are legal and write nothing.
+ *  - Stats: per_file[f] (nfiles entries, or NULL) is what sydelta_apply_delta_device reports
+ *    for file f (operations_count counts the delta's own ops); total (or NULL) is their sum.
+ *  - Stream order: the work is ordered on `stream` (NULL: the thread's library stream) and
+ *    the outputs are complete when the call returns.  The call waits for the stream once,
+ *    and for an upload slot only when the batch needs more table slices than the ring holds
+ *    (never once per file).
+ *  - Staging: consecutive ops that are contiguous in their source are merged on the host;
+ *    the merged table reaches the device through a per-thread ring of fixed-size pinned
+ *    slices (4 x 1 MiB, whatever the batch; released when the thread exits), the device copy
+ *    of it comes from the library's stream-ordered pool and is returned to it in stream
+ *    order. */
+int sydelta_apply_delta_batch_device(int device,
+        const uint8_t *d_basis, uint64_t basis_buf_len, const uint64_t *basis_off, const uint64_t *basis_len,
+        const sydelta_delta *const *deltas,
+        const uint8_t *d_lit, uint64_t lit_buf_len, const uint64_t *lit_off, const uint64_t *lit_len,
+        uint8_t *d_out, uint64_t out_buf_len, const uint64_t *out_off, const uint64_t *out_cap,
+        uint64_t nfiles, void *stream,
+        sydelta_apply_stats *per_file /* nfiles entries, or NULL */, sydelta_apply_stats *total /* or NULL */);
 
 /* ---------------------------------------------------------------------------
  * Chunk-sharded match of ONE large file over several devices (BASELINE config 5,

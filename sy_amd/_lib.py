@@ -99,6 +99,9 @@ SIGNATURES = [
     ("sydelta_delta_batch_get", _vp, [_vp, _u64]),
     ("sydelta_delta_batch_stats", _i, [_vp, ctypes.POINTER(MatchStatsC)]),
     ("sydelta_delta_batch_free", None, [_vp]),
+    ("sydelta_delta_batch_ptrs", _u64, [_vp, _vp, _u64]),
+    ("sydelta_apply_delta_batch_device", _i, [_i, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp,
+                                              _u64, _vp, _vp, ctypes.POINTER(DeltaStatsC)]),
     ("sydelta_chunk_classify", _i, [_vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _pp]),
     ("sydelta_chunk_walk", _i, [_vp, _u64, ctypes.POINTER(_u64), _pp]),
     ("sydelta_chunk_free", None, [_vp]),
@@ -160,13 +163,15 @@ def _load() -> ctypes.CDLL:
     for name, res, args in SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
-            # libsydelta.so must export every symbol.  The BLAKE3 entry points and the zstd
-            # decoder live in translation units of their own (sydelta_blake3.cpp,
-            # sydelta_unzstd_api.cpp); a library built from the
+            # libsydelta.so must export every symbol.  The BLAKE3 entry points, the zstd
+            # decoder and the batched apply live in translation units of their own
+            # (sydelta_blake3.cpp, sydelta_unzstd_api.cpp, sydelta_applybatch.cpp); a library
+            # built from the
             # other host units alone (the emulated-device build of the host-logic tests, loaded
             # through this table from another path) has none of them, and calling one there
             # raises AttributeError.
-            if name.startswith(("sydelta_blake3_", "sydelta_zstd_decompress_")) and LIB_PATH != os.path.join(HERE, "libsydelta.so"):
+            if name.startswith(("sydelta_blake3_", "sydelta_zstd_decompress_", "sydelta_apply_delta_batch_")) and \
+                    LIB_PATH != os.path.join(HERE, "libsydelta.so"):
                 continue
             raise ImportError(f"{LIB_PATH} does not export {name}")
         fn.restype = res

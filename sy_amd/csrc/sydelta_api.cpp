@@ -1508,6 +1508,11 @@ extern "C" uint64_t sydelta_delta_batch_count(const sydelta_delta_batch* b) { re
 extern "C" const sydelta_delta* sydelta_delta_batch_get(const sydelta_delta_batch* b, uint64_t i) {
     return (b && i < b->d.size()) ? &b->d[i] : nullptr;
 }
+extern "C" uint64_t sydelta_delta_batch_ptrs(const sydelta_delta_batch* b, const sydelta_delta** out, uint64_t cap) {
+    if (!b) return 0;
+    for (uint64_t i = 0; out && i < b->d.size() && i < cap; ++i) out[i] = &b->d[i];
+    return b->d.size();
+}
 extern "C" int sydelta_delta_batch_stats(const sydelta_delta_batch* b, sydelta_match_stats* out) try {
     if (!b || !out) return fail(SYDELTA_E_INVAL, "NULL argument");
     *out = b->total;

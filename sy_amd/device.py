@@ -354,6 +354,81 @@ def apply_device(basis: torch.Tensor, delta: DeviceDelta, lit: torch.Tensor, out
     return out[:st.bytes_written], {f: int(getattr(st, f)) for f, _ in _lib.DeltaStatsC._fields_}
 
 
+APPLY_STATS_DTYPE = np.dtype([("operations_count", "<u8"), ("literal_bytes", "<u8"), ("bytes_written", "<u8")])
+
+
+def apply_batch(basis: torch.Tensor, boffs, blens, deltas, lit: torch.Tensor, loffs, llens,
+                out: torch.Tensor | None = None, ooffs=None, stream=None):
+    """apply_delta for a batch in one call (sydelta_apply_delta_batch_device): file f's Copy
+    ops read basis[boffs[f] + offset, +size), its Data ops lit[loffs[f] + op.a, +op.b) (for a
+    batched match's deltas: the sources' offsets and lengths), its output goes to
+    out[ooffs[f], ...).  `deltas` is a DeltaBatch or a list of DeviceDelta.  With out=None an
+    arena is allocated and the outputs packed at 16-byte aligned offsets; with `out` given
+    and ooffs=None they are packed the same way into `out`.  File f may fill `out` up to the
+    next file's offset (the last one: to the end of `out`).
+    Returns (out, ooffs, per_file_stats): a structured array (APPLY_STATS_DTYPE)."""
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (boffs, blens, loffs, llens)]
+    own = []
+    if isinstance(deltas, DeltaBatch):
+        n = deltas.count
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        if int(lib.sydelta_delta_batch_ptrs(deltas.h, ptrs, n)) != n:
+            raise ValueError("delta batch changed size")
+        sizes = None
+    else:
+        n = len(deltas)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = np.zeros(n, dtype=np.uint64)
+        for f, d in enumerate(deltas):
+            k = len(d.kind)
+            sizes[f] = int(np.asarray(d.b, dtype=np.uint64).sum()) if k else 0
+            if d.handle is not None:  # the library's own delta: no copy of the ops
+                ptrs[f] = d.handle.h if isinstance(d.handle.h, int) else d.handle.h.value
+                continue
+            ops = np.zeros(k, dtype=_OP_DTYPE)
+            if k:
+                ops["kind"], ops["a"], ops["b"] = d.kind, d.a, d.b
+            h = lib.sydelta_delta_from_ops(ops.ctypes.data if k else None, k, d.source_size, d.block_size)
+            if not h:
+                for o in own:
+                    lib.sydelta_delta_free(o)
+                raise ValueError(f"file {f}: bad op array")
+            own.append(h)
+            ptrs[f] = h
+    try:
+        if any(len(a) != n for a in arrs):
+            raise ValueError("offset / length tables and deltas differ in length")
+        if ooffs is None:
+            if sizes is None:  # a DeltaBatch: the op arrays stay in the library
+                sizes = np.array([int(lib.sydelta_delta_source_size(ptrs[f])) for f in range(n)], dtype=np.uint64)
+            padded = (sizes + np.uint64(15)) & ~np.uint64(15)
+            ooffs = np.zeros(n, dtype=np.uint64)
+            if n > 1:
+                np.cumsum(padded[:-1], out=ooffs[1:])
+            need = int(ooffs[-1] + sizes[-1]) if n else 0
+        else:
+            ooffs = np.ascontiguousarray(ooffs, dtype=np.uint64)
+            if len(ooffs) != n:
+                raise ValueError("ooffs and deltas differ in length")
+            need = None
+        if out is None:
+            out = torch.empty(max(need, 1), dtype=torch.uint8, device=basis.device)
+        # file f's capacity: up to the next greater output offset (the last: the arena's end)
+        total = out.numel()
+        starts = np.append(np.unique(ooffs), np.uint64(total)).astype(np.uint64)
+        nxt = np.minimum(starts[np.searchsorted(starts[:-1], ooffs, side="right")], np.uint64(total))
+        ocaps = np.ascontiguousarray(nxt - np.minimum(ooffs, nxt), dtype=np.uint64)
+        stats = np.zeros(n, dtype=APPLY_STATS_DTYPE)
+        check(lib.sydelta_apply_delta_batch_device(
+            basis.device.index or 0, _ptr(basis), basis.numel(), arrs[0].ctypes.data, arrs[1].ctypes.data, ptrs,
+            _ptr(lit), lit.numel(), arrs[2].ctypes.data, arrs[3].ctypes.data, _ptr(out), total, ooffs.ctypes.data,
+            ocaps.ctypes.data, n, _stream(stream), stats.ctypes.data if n else None, None))
+    finally:
+        for o in own:
+            lib.sydelta_delta_free(o)
+    return out, ooffs, stats
+
+
 ZSTD_MAGIC = bytes([0x28, 0xB5, 0x2F, 0xFD])
 
 
