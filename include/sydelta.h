@@ -394,7 +394,8 @@ int sydelta_checksums_from_json(const char *json, uint64_t len, sydelta_block_ch
 int sydelta_delta_to_json(const sydelta_delta *d, const uint8_t *lit, uint64_t lit_len, char *buf, uint64_t cap,
                           uint64_t *out_len);
 /* The same text produced on the device from literal bytes in HBM (d_lit indexed by the
- * Data ops' source offsets) into d_out; *out_len as above (computed on the device). */
+ * Data ops' source offsets) into d_out; *out_len as above (computed on the device).
+ * d_lit and d_out may have any alignment. */
 int sydelta_delta_to_json_device(const sydelta_delta *d, const uint8_t *d_lit, uint64_t lit_len, uint8_t *d_out,
                                  uint64_t out_cap, uint64_t *out_len, void *stream);
 /* serde_json::to_string(&Vec<BlockChecksum>) of a signature in HBM, written on the device:
@@ -421,8 +422,9 @@ int sydelta_checksums_from_json_device(const uint8_t *d_text, uint64_t len, syde
  * delta's literal bytes; with d_lit (device, lit_cap >= *lit_len) they are written there
  * in op order, and *out (when not NULL) receives the ops, source_size and block_size,
  * its Data ops indexing d_lit (op.a = offset of the first byte) as
- * sydelta_apply_delta_device reads them.  Any other spelling returns SYDELTA_E_INVAL
- * naming the first byte that breaks the form: parse those with sydelta_delta_from_json. */
+ * sydelta_apply_delta_device reads them.  d_text and d_lit may have any alignment.  Any
+ * other spelling returns SYDELTA_E_INVAL naming the first byte that breaks the form: parse
+ * those with sydelta_delta_from_json. */
 int sydelta_delta_from_json_device(const uint8_t *d_text, uint64_t len, uint8_t *d_lit, uint64_t lit_cap,
                                    uint64_t *lit_len, sydelta_delta **out, void *stream);
 /* The zstd frame (RFC 8878) of d_in[0, len) into d_out, on the device: what ssh.rs:1009-1017

@@ -3655,10 +3655,11 @@ __global__ __launch_bounds__(256) void k_sigparse(const uint8_t* __restrict__ t,
 // there (LdsText) and anything outside the staged span from global memory.  Round 3 ran
 // the same bodies on global memory, one byte load per character per thread with the
 // lanes 64 bytes apart: 113 GB/s of text over the three kernels.
-constexpr uint32_t kDpRow = 68;                          // LDS bytes per staged 64-byte row
-constexpr uint32_t kDpBefore = 8;                        // bytes staged before the wave's first chunk
-constexpr uint32_t kDpSpan = 64 * 64 + kDpBefore + 136;  // staged bytes per wave
-constexpr uint32_t kDpRows = (kDpSpan + 63) / 64;
+using dparse::kDpBefore;
+using dparse::kDpLitMax;
+using dparse::kDpRow;
+using dparse::kDpRows;
+using dparse::kDpSpan;
 
 // The text outside the staged span (not reached by well-formed text: every token and its
 // look-ahead ends inside the 136-byte halo).  Not inlined, so that the compiler cannot
@@ -3670,92 +3671,48 @@ struct LdsText {
     uint64_t p0, n;     // staged text [p0, p0 + n)
     __device__ __forceinline__ uint8_t operator[](uint64_t p) const {
         const uint64_t d = p - p0;
-        if (__builtin_expect(d < n, 1)) return l[(d >> 6) * kDpRow + (d & 63)];
+        if (__builtin_expect(d < n, 1)) return l[dparse::stage_off(d)];
         return dp_gload(g, p);
     }
 };
 
-// The fast path of the three kernels: a chunk of 64 digits and commas (inside a Data
-// op's literal run: almost all of a literal-heavy delta's text) is classified with SWAR
-// masks from 18 dwords of the staged rows instead of byte by byte.  DpFast.ok: the chunk
-// is such a chunk, every literal starting in it is 1-3 digits without a leading zero,
-// <= 255, followed by ',' and a digit (all checked here, with 8 bytes of look-ahead), so
-// chunk_count / chunk_parse would find exactly these literals and nothing else; any other
-// chunk (ops, the end of a run, a bad byte) takes the bodies.
+// The fast path of the three kernels (sydelta_dparse.hpp fast_chunk / fast_classify): a
+// chunk of 64 digits and commas is classified with SWAR masks from 18 dwords of the
+// staged rows instead of byte by byte.  DpFast.ok: chunk_count / chunk_parse would find
+// exactly the literals of DpFast.lits and nothing else; any other chunk takes the bodies.
 struct DpFast {
     bool ok;
     uint64_t lits;  // bit i: a literal starts at byte i of the chunk
     uint32_t x[18]; // the chunk's 64 bytes and 8 bytes of look-ahead
 };
-__device__ __forceinline__ uint32_t dp_bits4(uint32_t m) {  // bit 7 of each byte -> bits 0..3
-    return ((m >> 7) & 1u) | ((m >> 14) & 2u) | ((m >> 21) & 4u) | ((m >> 28) & 8u);
-}
-__device__ __forceinline__ uint32_t dp_digits4(uint32_t x) {
-    const uint32_t t = x ^ 0x30303030u;
-    return dp_bits4(~(((t & 0x7F7F7F7Fu) + 0x76767676u) | t) & 0x80808080u);
-}
-__device__ __forceinline__ uint32_t dp_eq4(uint32_t x, uint32_t pat) {
-    const uint32_t y = x ^ pat;
-    return dp_bits4(~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u);
-}
 __device__ __forceinline__ void dp_fast(const dparse::DArgs& a, const LdsText& t, uint64_t c, DpFast& f) {
     f.ok = false;
     f.lits = 0;
-    const uint64_t lo = dparse::chunk_lo(a, c);
-    if (c == 0 || lo + 72 > a.e) return;  // the first chunk, the tail: the bodies
-    const uint32_t d0 = (uint32_t)(lo - t.p0);  // 8 + 64 * lane: dword-aligned, inside one row each
-    if (d0 + 72 > t.n) return;
+    uint32_t d0;
+    if (!dparse::fast_chunk(a, c, t.p0, t.n, d0)) return;
     typedef __attribute__((address_space(3))) const uint32_t lds_u32;
 #pragma unroll
-    for (int k = 0; k < 18; ++k) {
-        const uint32_t dd = d0 + 4 * k;
-        f.x[k] = *(lds_u32*)(t.l + (dd >> 6) * kDpRow + (dd & 63));
-    }
-    const uint32_t dp = d0 - 4;
-    const uint32_t prevw = *(lds_u32*)(t.l + (dp >> 6) * kDpRow + (dp & 63));
-    uint64_t D = 0, C = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        D |= (uint64_t)dp_digits4(f.x[k]) << (4 * k);
-        C |= (uint64_t)dp_eq4(f.x[k], 0x2C2C2C2Cu) << (4 * k);
-    }
-    if ((D | C) != ~0ull) return;
-    const uint32_t DL = dp_digits4(f.x[16]) | (dp_digits4(f.x[17]) << 4);  // look-ahead bytes 64..71
-    const uint32_t CL = dp_eq4(f.x[16], 0x2C2C2C2Cu) | (dp_eq4(f.x[17], 0x2C2C2C2Cu) << 4);
-    const uint32_t pb = prevw >> 24;
-    const uint64_t L = D & ((C << 1) | (uint64_t)(pb == ',' || pb == '['));
-    // digits / commas at i+1, i+2, i+3 (with the look-ahead)
-    const uint64_t D1 = (D >> 1) | ((uint64_t)DL << 63), D2 = (D >> 2) | ((uint64_t)DL << 62),
-                   D3 = (D >> 3) | ((uint64_t)DL << 61), D4 = (D >> 4) | ((uint64_t)DL << 60);
-    const uint64_t C1 = (C >> 1) | ((uint64_t)CL << 63), C2 = (C >> 2) | ((uint64_t)CL << 62),
-                   C3 = (C >> 3) | ((uint64_t)CL << 61);
-    // 1 digit: ',' then a digit; 2: digit, ',', digit; 3: digit, digit, ',', digit; 4+: bad
-    const uint64_t len1 = ~D1, len2 = D1 & ~D2, len3 = D1 & D2 & ~D3;
-    const uint64_t follow = (len1 & C1 & D2) | (len2 & C2 & D3) | (len3 & C3 & D4);
-    if (L & ~follow) return;
-    f.lits = L;
-    f.ok = true;  // values (<= 255, no leading zero) are checked while they are written
+    for (int k = 0; k < 18; ++k) f.x[k] = *(lds_u32*)(t.l + dparse::stage_off(d0 + 4 * k));
+    const uint32_t prevw = *(lds_u32*)(t.l + dparse::stage_off(d0 - 4));
+    f.ok = dparse::fast_classify(f.x, prevw >> 24, f.lits);  // values: fast_values, while they are written
 }
-// Byte i of the fast chunk (constant i after unrolling).
-__device__ __forceinline__ uint32_t dp_byte(const DpFast& f, int i) { return (f.x[i >> 2] >> (8 * (i & 3))) & 0xFFu; }
 
 // Stage this wave's span (chunks c0 .. c0 + 63) and return its accessor.
 __device__ __forceinline__ LdsText dp_stage(const dparse::DArgs& a, uint64_t c0, uint8_t* rows) {
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t p0 = dparse::chunk_lo(a, c0) - kDpBefore;  // >= 0: chunk 0 starts at kHead = 8
-    const uint64_t hi = p0 + kDpSpan < a.e ? p0 + kDpSpan : a.e;
-    const uint32_t n = (uint32_t)(hi - p0);
+    const uint64_t p0 = dparse::stage_p0(a, c0);
+    const uint32_t n = dparse::stage_len(a, p0);
     const uint8_t* g = a.t + p0;
     if (((uintptr_t)g & 3) == 0) {
         for (uint32_t i = 4 * lane; i < n; i += 256) {
             if (i + 4 <= n) {
-                *(uint32_t*)(rows + (i >> 6) * kDpRow + (i & 63)) = *(const uint32_t*)(g + i);
+                *(uint32_t*)(rows + dparse::stage_off(i)) = *(const uint32_t*)(g + i);
             } else {
-                for (uint32_t j = i; j < n; ++j) rows[(j >> 6) * kDpRow + (j & 63)] = g[j];
+                for (uint32_t j = i; j < n; ++j) rows[dparse::stage_off(j)] = g[j];
             }
         }
     } else {
-        for (uint32_t i = lane; i < n; i += 64) rows[(i >> 6) * kDpRow + (i & 63)] = g[i];
+        for (uint32_t i = lane; i < n; i += 64) rows[dparse::stage_off(i)] = g[i];
     }
     lds_fence();
     return LdsText{a.t, (const lds_u8*)rows, p0, n};
@@ -3803,7 +3760,6 @@ __global__ __launch_bounds__(256) void k_dparse_place(dparse::DArgs a, const uin
 // partial dwords at its two ends byte by byte (they may be shared with the neighbouring
 // waves' ranges).  Byte stores from 64 lanes 18 bytes apart made the round-3 kernel's
 // literal output the bulk of its time.
-constexpr uint32_t kDpLitMax = 64 * (dparse::kChunk / 2);
 struct LdsLit {
     __attribute__((address_space(3))) uint8_t* l;
     uint64_t base;  // output index of l[0]
@@ -3830,22 +3786,12 @@ __global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t*
         DpFast f;
         dp_fast(a, t, c, f);
         if (f.ok) {  // each literal's value; a leading zero or a value > 255 sends the chunk to the body
-            const uint64_t r0 = lrank[c];
-            bool good = true;
-#pragma unroll
-            for (int i = 0; i < 64; ++i) {
-                if (!((f.lits >> i) & 1)) continue;
-                const uint32_t b0 = dp_byte(f, i) - '0', b1 = dp_byte(f, i + 1) - '0', b2 = dp_byte(f, i + 2) - '0';
-                const bool two = b1 < 10, three = two && b2 < 10;
-                const uint32_t v = three ? b0 * 100 + b1 * 10 + b2 : two ? b0 * 10 + b1 : b0;
-                good &= v <= 255 && !(two && b0 == 0);
-                const uint64_t r = r0 + __popcll(f.lits & ((1ull << i) - 1));
+            f.ok = dparse::fast_values(f.x, f.lits, lrank[c], [&](uint64_t r, uint32_t v) {
                 if (lit) {
                     if (staged) lo[wid][r - l0] = (uint8_t)v;
                     else lit[r] = (uint8_t)v;
                 }
-            }
-            f.ok = good;
+            });
         }
         if (!f.ok) {
             uint64_t b;
@@ -3862,10 +3808,8 @@ __global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t*
     // [l0, l1): head bytes up to a dword boundary (of the absolute address), whole dwords,
     // tail bytes
     const uint8_t* src = lo[wid];
-    const int64_t ph = (int64_t)((uintptr_t)lit & 3);
-    const uint64_t a0 = (uint64_t)((((int64_t)l0 + ph + 3) & ~3ll) - ph);
-    const int64_t a1s = (((int64_t)l1 + ph) & ~3ll) - ph;
-    const uint64_t a1 = a1s < (int64_t)a0 ? a0 : (uint64_t)a1s;
+    uint64_t a0, a1;
+    dparse::lit_split(l0, l1, (uint32_t)((uintptr_t)lit & 3), a0, a1);
     if (a0 >= a1) {
         for (uint64_t i = l0 + lane; i < l1; i += 64) lit[i] = src[i - l0];
         return;
@@ -4010,7 +3954,10 @@ __global__ __launch_bounds__(256) void k_json_write(const JsonPiece* __restrict_
     __syncthreads();
     uint32_t pre = inc - mine;
     for (uint32_t q = 0; q < wid; ++q) pre += wsum[q];
-    const uint32_t ph = (uint32_t)(dst & 15);  // LDS byte k <-> global byte (dst & ~15) + k
+    // LDS byte k <-> the byte at (address of out[dst] & ~15) + k: the granules are those of
+    // the absolute address (as k_apply's and k_sigjson_write's), so d_out may start anywhere
+    const uintptr_t oaddr = (uintptr_t)(out + dst);
+    const uint32_t ph = (uint32_t)(oaddr & 15);
     uint32_t head = ph;
     if (P.flags & kJsonSep) head += 1;
     if (P.flags & kJsonFirst) head += 9;
@@ -4051,7 +3998,7 @@ __global__ __launch_bounds__(256) void k_json_write(const JsonPiece* __restrict_
     }
     __syncthreads();
     // LDS [ph, end) -> out [dst, dst + end - ph)
-    uint8_t* g = out + (dst & ~15ull);
+    uint8_t* g = out + dst - ph;  // 16-byte aligned; derived from out, so the stores stay global ones
     for (uint32_t c = 16 * threadIdx.x; c < end; c += 16 * blockDim.x) {
         if (c >= ph && c + 16 <= end) {
             *(uint4*)(g + c) = *(const uint4*)(js + c);

@@ -412,6 +412,57 @@ def dparse_checks():
             assert compact(*got) == t, t
             assert got == expect(t) == wire.delta_from_json(t), t
         n_checks += 1
+
+    # The independent reference of the GPU tests (tests/delta_json_ref.py) against the
+    # library on the emulated device (the kernels' wave form, tests/csrc/dparse_wave.hpp):
+    # accepted exactly when parse_ref accepts, with an equal parse; a refused text named
+    # at first_bad, in all three call shapes; on the small spellings above and on the long
+    # texts of test_gpu_dparse_edges.py (ends near wave boundaries, the longest token across
+    # them, literal densities, bytes changed inside the chunks the fast path owns).
+    import delta_json_cases as cases
+    from delta_json_ref import first_bad, first_bad_re, parse_ref
+    from sy_amd._lib import SYDELTA_E_INVAL
+
+    def dev_bad(text: bytes, lit_mode: str):
+        """The position in the library's error text (None: accepted), for the length
+        query, validate-only with a delta handle, or the full call."""
+        buf = np.frombuffer(text, np.uint8).copy() if text else np.zeros(1, np.uint8)
+        n, h = ctypes.c_uint64(), ctypes.c_void_p()
+        lit = np.zeros(len(text) // 2 + 1, np.uint8)  # >= any literal count
+        rc = lib.sydelta_delta_from_json_device(
+            ctypes.c_void_p(buf.ctypes.data), len(text), ctypes.c_void_p(lit.ctypes.data) if lit_mode == "full" else None,
+            lit.size if lit_mode == "full" else 0, ctypes.byref(n), None if lit_mode == "query" else ctypes.byref(h), None)
+        if rc == 0:
+            if h:
+                lib.sydelta_delta_free(h)
+            return None
+        assert rc == SYDELTA_E_INVAL, rc
+        msg = lib.sydelta_last_error().decode()
+        assert "not serde's compact form at byte " in msg, msg
+        return int(msg.rsplit(" ", 1)[1])
+
+    def check_against_ref(t: bytes, bad_ref):
+        nonlocal n_checks
+        ref = parse_ref(t)
+        assert (ref is None) == (bad_ref is not None), (t[:80], bad_ref)
+        for mode in ("query", "validate", "full"):
+            assert dev_bad(t, mode) == bad_ref, (t[:80], mode, bad_ref)
+        if ref is not None:
+            assert dev_parse(t) == ref, t[:80]
+        n_checks += 1
+
+    for t in [compact(*c) for c in cases.small_accepted()] + cases.small_refused() + bad:
+        assert first_bad_re(t) == first_bad(t), t
+        check_against_ref(t, first_bad(t))
+    for gen in (cases.end_cases, cases.density_cases, cases.boundary_cases):
+        for _, _, t in gen():
+            check_against_ref(t, first_bad_re(t))
+    _, base, r0, r1 = cases.refuse_base()
+    for chunk in cases.target_chunks(base, r0, r1).values():
+        for _, _, t in cases.deterministic_changes(base, chunk):
+            check_against_ref(t, first_bad_re(t))
+    for t in cases.random_changes(base, 300, 99):
+        check_against_ref(t, first_bad_re(t))
     return n_checks
 
 

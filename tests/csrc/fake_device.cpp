@@ -27,6 +27,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "dparse_wave.hpp"
 #include "sydelta_internal.hpp"
 
 extern "C" uint64_t oracle_xxh3_64(const uint8_t* in, uint64_t len);
@@ -512,26 +513,25 @@ hipError_t launch_sigparse(const uint8_t* d_text, uint64_t len, const uint64_t* 
     }
     return hipSuccess;
 }
-// K7d: sydelta_dparse.hpp's chunk bodies per chunk (parse in descending chunk order).
+// K7d: the kernels' wave form (dparse_wave.hpp: staged rows, the fast path or
+// sydelta_dparse.hpp's chunk bodies, the literal slab and its dword stores), waves and
+// lanes in descending order.
 hipError_t launch_dparse_count(const dparse::DArgs& a, uint64_t* d_ocnt, uint64_t* d_lcnt, hipStream_t, Profiler*) {
     EmuTimer emu_t;
-    for (uint64_t c = 0; c < a.nc; ++c) dparse::chunk_count(a, c, d_ocnt[c], d_lcnt[c]);
+    dparse_wave::count(a, d_ocnt, d_lcnt);
     return hipSuccess;
 }
 hipError_t launch_dparse_place(const dparse::DArgs& a, const uint64_t* d_orank, uint64_t* d_pos, hipStream_t,
                                Profiler*) {
     EmuTimer emu_t;
-    for (uint64_t c = 0; c < a.nc; ++c) dparse::chunk_place(a, c, d_orank[c], d_pos);
+    dparse_wave::place(a, d_orank, d_pos);
     return hipSuccess;
 }
 hipError_t launch_dparse(const dparse::DArgs& a, const uint64_t* d_orank, const uint64_t* d_lrank, const uint64_t* d_pos,
                          uint64_t nops, sydelta_op* d_ops, uint8_t* d_lit, unsigned long long* d_bad, hipStream_t,
                          Profiler*) {
     EmuTimer emu_t;
-    for (uint64_t c = a.nc; c-- > 0;) {
-        const uint64_t b = dparse::chunk_parse(a, c, d_orank, d_lrank, d_pos, nops, d_ops, d_lit);
-        if (b < *d_bad) *d_bad = b;
-    }
+    dparse_wave::parse(a, d_orank, d_lrank, d_pos, nops, d_ops, d_lit, d_bad);
     return hipSuccess;
 }
 // K5b: the kernels' own per-thread bodies (sydelta_chain.hpp) in the launch order of

@@ -22,7 +22,11 @@
 //  * its parse (K7p): texts in exact-size arrays parse back to their signature, and a
 //    mutated text is refused or is the compact text of what it parses to;
 //  * the Delta JSON parse (sydelta_dparse.hpp, K7d): the same two properties for the ops
-//    region of random deltas' compact text.
+//    region of random deltas' compact text; and every parse also goes through the
+//    kernels' wave form (dparse_wave.hpp: the staged rows with both copy paths, the SWAR
+//    fast path, the literal slab and its dword stores at output phases 0..3), which must
+//    leave the same counts, ops, literals and bad position as the plain bodies; literal
+//    runs over several waves with one byte changed inside the chunks the fast path owns.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,6 +42,7 @@
 #include "sydelta_chain.hpp"
 #include "sydelta_sigjson.hpp"
 #include "sydelta_dparse.hpp"
+#include "dparse_wave.hpp"
 #include "sydelta_walk.hpp"
 #include "sydelta_zstd.hpp"
 
@@ -518,37 +523,159 @@ static std::string dops_text(const std::vector<DOp>& v) {
     }
     return t;
 }
-// Parse the ops region of text (head, region, tail) with the chunk bodies; false if refused.
-static bool dparse_all(const std::string& text, std::vector<DOp>& out) {
-    const std::string key = "],\"source_size\":";
-    const size_t at = text.rfind(key);
-    if (text.size() < 8 || at == std::string::npos || at < 8 || text.compare(0, 8, "{\"ops\":[") != 0) return false;
+// One parse of a text's ops region: what the three kernels leave behind.
+struct DRun {
+    uint64_t nops = 0, nlit = 0, bad = dparse::kNoBad;  // bad: the smallest bad position
+    std::vector<uint64_t> ocnt, lcnt;                   // per chunk
+    std::vector<sydelta_op> ops;
+    std::vector<uint8_t> lit;
+    bool ok() const { return bad == dparse::kNoBad; }
+};
+static bool dparse_region(const std::string& text, size_t& at) {
+    at = text.rfind("],\"source_size\":");
+    return text.size() >= 8 && at != std::string::npos && at >= 8 && text.compare(0, 8, "{\"ops\":[") == 0;
+}
+static void dparse_ranks(const DRun& r, std::vector<uint64_t>& orank, std::vector<uint64_t>& lrank) {
+    const size_t nc = r.ocnt.size();
+    orank.assign(nc + 1, 0);
+    lrank.assign(nc + 1, 0);
+    for (size_t c = 0; c < nc; ++c) {
+        orank[c + 1] = orank[c] + r.ocnt[c];
+        lrank[c + 1] = lrank[c] + r.lcnt[c];
+    }
+}
+// The chunk bodies on plain memory, every chunk on its own (the text in an array of
+// exactly its length).
+static void dparse_plain(const std::string& text, size_t at, DRun& r) {
     const uint64_t len = text.size();
     std::unique_ptr<uint8_t[]> t(new uint8_t[len]);
     memcpy(t.get(), text.data(), len);
     const dparse::DArgs a{t.get(), at, (at - 8 + dparse::kChunk - 1) / dparse::kChunk};
-    std::vector<uint64_t> orank(a.nc + 1, 0), lrank(a.nc + 1, 0);
-    for (uint64_t c = 0; c < a.nc; ++c) {
-        uint64_t no, nl;
-        dparse::chunk_count(a, c, no, nl);
-        orank[c + 1] = orank[c] + no;
-        lrank[c + 1] = lrank[c] + nl;
+    r.ocnt.assign(a.nc, 0);
+    r.lcnt.assign(a.nc, 0);
+    for (uint64_t c = 0; c < a.nc; ++c) dparse::chunk_count(a, c, r.ocnt[c], r.lcnt[c]);
+    std::vector<uint64_t> orank, lrank;
+    dparse_ranks(r, orank, lrank);
+    r.nops = orank[a.nc];
+    r.nlit = lrank[a.nc];
+    if (a.nc && !r.nops) {
+        r.bad = 8;
+        return;
     }
-    const uint64_t nops = orank[a.nc], nlit = lrank[a.nc];
-    if (a.nc && !nops) return false;
-    std::unique_ptr<uint64_t[]> pos(new uint64_t[nops ? nops : 1]);
-    std::unique_ptr<sydelta_op[]> ops(new sydelta_op[nops ? nops : 1]);
-    std::unique_ptr<uint8_t[]> lit(new uint8_t[nlit ? nlit : 1]);
+    std::unique_ptr<uint64_t[]> pos(new uint64_t[r.nops ? r.nops : 1]);
+    std::unique_ptr<sydelta_op[]> ops(new sydelta_op[r.nops ? r.nops : 1]);
+    std::unique_ptr<uint8_t[]> lit(new uint8_t[r.nlit ? r.nlit : 1]);
     for (uint64_t c = 0; c < a.nc; ++c) dparse::chunk_place(a, c, orank[c], pos.get());
     for (uint64_t c = a.nc; c-- > 0;)
-        if (dparse::chunk_parse(a, c, orank.data(), lrank.data(), pos.get(), nops, ops.get(), lit.get()) != dparse::kNoBad)
-            return false;
+        r.bad = std::min(r.bad, dparse::chunk_parse(a, c, orank.data(), lrank.data(), pos.get(), r.nops, ops.get(), lit.get()));
+    r.ops.assign(ops.get(), ops.get() + r.nops);
+    r.lit.assign(lit.get(), lit.get() + r.nlit);
+}
+// The kernels' wave form (dparse_wave.hpp): the text in an array that ends with it, at
+// address phase tph (the dword or the byte copy of the staging); the literals into an
+// array that ends with them, at address phase lph, the lph bytes before them guarded; a
+// second pass with lit NULL (validate only) must name the same position.  *fast: chunks
+// classified by the fast path.
+static void dparse_waves(const std::string& text, size_t at, unsigned tph, unsigned lph, DRun& r, uint64_t* fast) {
+    const uint64_t len = text.size();
+    std::unique_ptr<uint8_t[]> tb(new uint8_t[len + tph]);
+    uint8_t* t = tb.get() + tph;
+    memcpy(t, text.data(), len);
+    const dparse::DArgs a{t, at, (at - 8 + dparse::kChunk - 1) / dparse::kChunk};
+    std::unique_ptr<uint64_t[]> ocnt(new uint64_t[a.nc ? a.nc : 1]), lcnt(new uint64_t[a.nc ? a.nc : 1]);
+    dparse_wave::count(a, ocnt.get(), lcnt.get(), fast);
+    r.ocnt.assign(ocnt.get(), ocnt.get() + a.nc);
+    r.lcnt.assign(lcnt.get(), lcnt.get() + a.nc);
+    std::vector<uint64_t> orank, lrank;
+    dparse_ranks(r, orank, lrank);
+    r.nops = orank[a.nc];
+    r.nlit = lrank[a.nc];
+    if (a.nc && !r.nops) {
+        r.bad = 8;
+        return;
+    }
+    std::unique_ptr<uint64_t[]> pos(new uint64_t[r.nops ? r.nops : 1]);
+    std::unique_ptr<sydelta_op[]> ops(new sydelta_op[r.nops ? r.nops : 1]);
+    std::unique_ptr<uint8_t[]> lb(new uint8_t[r.nlit + lph]);
+    uint8_t* lit = lb.get() + lph;
+    CHECK(((uintptr_t)lit & 3) == (lph & 3) && ((uintptr_t)t & 3) == (tph & 3));
+    memset(lb.get(), 0xEE, r.nlit + lph);
+    dparse_wave::place(a, orank.data(), pos.get());
+    unsigned long long bad = dparse::kNoBad, bad_v = dparse::kNoBad;
+    dparse_wave::parse(a, orank.data(), lrank.data(), pos.get(), r.nops, ops.get(), lit, &bad);
+    for (unsigned k = 0; k < lph; ++k) CHECK(lb[k] == 0xEE);  // nothing before lit[0]
+    std::unique_ptr<sydelta_op[]> ops_v(new sydelta_op[r.nops ? r.nops : 1]);
+    dparse_wave::parse(a, orank.data(), lrank.data(), pos.get(), r.nops, ops_v.get(), nullptr, &bad_v);
+    CHECK(bad == bad_v);
+    r.bad = bad;
+    r.ops.assign(ops.get(), ops.get() + r.nops);
+    r.lit.assign(lit, lit + r.nlit);
+    if (r.ok())
+        for (uint64_t i = 0; i < r.nops; ++i)
+            CHECK(ops[i].kind == ops_v[i].kind && ops[i].a == ops_v[i].a && ops[i].b == ops_v[i].b);
+}
+// Chunk by chunk: where the classifier says yes, chunk_count finds no op start and
+// popcount(lits) literal starts; and chunk_parse finds no bad position and the same values
+// exactly when fast_values finds every value in range.
+static void dparse_classifier(const std::string& text, size_t at, const DRun& plain) {
+    if (plain.ocnt.empty() || !plain.nops) return;
+    const uint64_t len = text.size();
+    std::unique_ptr<uint8_t[]> t(new uint8_t[len]);
+    memcpy(t.get(), text.data(), len);
+    const dparse::DArgs a{t.get(), at, (at - 8 + dparse::kChunk - 1) / dparse::kChunk};
+    std::vector<uint64_t> orank, lrank;
+    dparse_ranks(plain, orank, lrank);
+    std::unique_ptr<uint64_t[]> pos(new uint64_t[plain.nops]);
+    std::unique_ptr<sydelta_op[]> ops(new sydelta_op[plain.nops]);
+    std::unique_ptr<uint8_t[]> lit(new uint8_t[plain.nlit ? plain.nlit : 1]);
+    for (uint64_t c = 0; c < a.nc; ++c) dparse::chunk_place(a, c, orank[c], pos.get());
+    dparse_wave::Wave w;
+    for (uint64_t c0 = 0; c0 < a.nc; c0 += 64) {
+        w.stage(a, c0);
+        for (uint64_t c = c0; c < std::min(a.nc, c0 + 64); ++c) {
+            uint32_t x[18];
+            uint64_t lits;
+            if (!w.fast(a, c, x, lits)) continue;
+            uint64_t no, nl;
+            dparse::chunk_count(a, c, no, nl);
+            CHECK(no == 0 && nl == (uint64_t)__builtin_popcountll(lits));
+            std::vector<uint8_t> vals;
+            const bool good = dparse::fast_values(x, lits, 0, [&](uint64_t r, uint32_t v) {
+                CHECK(r == vals.size());
+                vals.push_back((uint8_t)v);
+            });
+            CHECK(vals.size() == nl);
+            const uint64_t b = dparse::chunk_parse(a, c, orank.data(), lrank.data(), pos.get(), plain.nops, ops.get(), lit.get());
+            CHECK(good == (b == dparse::kNoBad));
+            if (good) CHECK(memcmp(lit.get() + lrank[c], vals.data(), nl) == 0);
+        }
+    }
+}
+// Parse the ops region of text (head, region, tail) with the chunk bodies and with the
+// kernels' wave form, which must agree on every count, op, literal and on the bad
+// position; false if refused (*bad_out: where).
+static uint64_t g_dwave_fast = 0, g_dwave_runs = 0;
+static bool dparse_all(const std::string& text, std::vector<DOp>& out, uint64_t* bad_out = nullptr) {
+    size_t at;
+    if (!dparse_region(text, at)) return false;
+    DRun p, w;
+    dparse_plain(text, at, p);
+    const unsigned tph = (unsigned)(g_dwave_runs % 5), lph = (unsigned)((g_dwave_runs / 5) % 4);  // text at 0..4, literals at 0..3
+    ++g_dwave_runs;
+    dparse_waves(text, at, tph, lph, w, &g_dwave_fast);
+    CHECK(p.ocnt == w.ocnt && p.lcnt == w.lcnt && p.nops == w.nops && p.nlit == w.nlit);
+    CHECK(p.bad == w.bad);
+    dparse_classifier(text, at, p);
+    if (bad_out) *bad_out = p.bad;
+    if (!p.ok()) return false;
+    CHECK(p.lit == w.lit);
     out.clear();
-    for (uint64_t i = 0; i < nops; ++i) {
-        DOp d{ops[i].kind == SYDELTA_OP_COPY, ops[i].a, ops[i].b, {}};
+    for (uint64_t i = 0; i < p.nops; ++i) {
+        CHECK(p.ops[i].kind == w.ops[i].kind && p.ops[i].a == w.ops[i].a && p.ops[i].b == w.ops[i].b);
+        DOp d{p.ops[i].kind == SYDELTA_OP_COPY, p.ops[i].a, p.ops[i].b, {}};
         if (!d.copy) {
-            CHECK(ops[i].a + ops[i].b <= nlit);
-            d.lit.assign(lit.get() + ops[i].a, lit.get() + ops[i].a + ops[i].b);
+            CHECK(p.ops[i].a + p.ops[i].b <= p.nlit);
+            d.lit.assign(p.lit.begin() + p.ops[i].a, p.lit.begin() + p.ops[i].a + p.ops[i].b);
         }
         out.push_back(d);
     }
@@ -603,6 +730,83 @@ static void dparse_case(std::mt19937_64& rng, uint64_t* accepted, uint64_t* refu
     }
 }
 
+// K7d's wave form on what only it sees: a literal run over several waves (Copy, one Data
+// op of 4000-9000 literals, Copy; dense, sparse or mixed values), whose chunks the fast
+// path owns, with one byte changed inside the run -- a value made 256..999, a leading
+// zero, ',' -> a digit (a literal of 4+ digits), a digit -> ',' (an empty element), any
+// byte -> a byte no literal run holds -- or 1-3 random bytes anywhere.  dparse_all holds
+// the wave form to the plain bodies on each; an accepted text is the compact text of its
+// parse.
+static void dwave_case(std::mt19937_64& rng, uint64_t* accepted, uint64_t* refused) {
+    std::vector<DOp> v(3);
+    v[0] = DOp{true, rng() % 1000, 4096, {}};
+    v[2] = DOp{true, ~0ull, ~0ull, {}};
+    v[1].copy = false;
+    v[1].lit.resize(4000 + rng() % 5000);
+    const int density = (int)(rng() % 3);
+    static const uint8_t edge[] = {0, 9, 10, 99, 100, 199, 200, 255};
+    for (auto& b : v[1].lit) b = density == 0 ? (uint8_t)(rng() % 10) : density == 1 ? (uint8_t)(100 + rng() % 156) : edge[rng() % 8];
+    const std::string text = "{\"ops\":[" + dops_text(v) + "],\"source_size\":123,\"block_size\":4096}";
+    const size_t r0 = text.find("[", 9) + 1, r1 = text.find("]", r0);  // the run's digits and commas
+    std::vector<DOp> back;
+    CHECK(dparse_all(text, back) && back.size() == 3 && back[1].lit == v[1].lit);
+    static const char other[] = "{}[]:\"-.ea \0\x80\xff";
+    for (int m = 0; m < 40; ++m) {
+        std::string t = text;
+        const int kind = m % 8;
+        // a position of the wanted class near a random point of the run
+        auto find_from = [&](auto pred) {
+            size_t p = r0 + rng() % (r1 - r0);
+            for (size_t k = 0; k < r1 - r0; ++k, p = p + 1 < r1 ? p + 1 : r0)
+                if (pred(p)) return p;
+            return (size_t)0;
+        };
+        auto digit = [&](size_t p) { return t[p] >= '0' && t[p] <= '9'; };
+        auto lit_len = [&](size_t p) {  // digits of the literal starting at p, 0 if none starts there
+            if (!digit(p) || digit(p - 1)) return 0;
+            int k = 1;
+            while (digit(p + k)) ++k;
+            return k;
+        };
+        size_t p = 0;
+        if (kind == 0) {  // 256..999
+            if ((p = find_from([&](size_t q) { return lit_len(q) == 3; }))) {
+                t[p] = (char)('3' + rng() % 7);
+            } else if ((p = find_from([&](size_t q) { return lit_len(q) == 1 && t[q + 1] == ',' && lit_len(q + 2) == 1; }))) {
+                t[p + 1] = '5';  // "a,b" -> "a5b" for a >= 3
+                t[p] = (char)('3' + rng() % 7);
+            }
+        } else if (kind == 1) {  // a leading zero
+            if ((p = find_from([&](size_t q) { return lit_len(q) >= 2; }))) t[p] = '0';
+            else if ((p = find_from([&](size_t q) { return lit_len(q) == 1 && t[q + 1] == ',' && lit_len(q + 2) == 1; }))) {
+                t[p] = '0';
+                t[p + 1] = '0';
+            }
+        } else if (kind == 2) {  // ',' -> a digit
+            if ((p = find_from([&](size_t q) { return t[q] == ','; }))) t[p] = (char)('0' + rng() % 10);
+        } else if (kind == 3) {  // a digit -> ','
+            if ((p = find_from(digit))) t[p] = ',';
+        } else if (kind < 6) {  // a byte of no literal run
+            p = r0 + rng() % (r1 - r0);
+            t[p] = other[rng() % (sizeof other - 1)];
+        } else {
+            for (int j = 0, k = 1 + (int)(rng() % 3); j < k; ++j)
+                t[8 + rng() % (t.size() - 8)] = "0123456789,,,,{}[]:\"aDC -"[rng() % 25];
+        }
+        std::vector<DOp> got;
+        const bool acc = dparse_all(t, got);
+        if (acc) {
+            const size_t at = t.rfind("],\"source_size\":");
+            CHECK(t.substr(8, at - 8) == dops_text(got));
+            ++*accepted;
+        } else {
+            ++*refused;
+        }
+        // > 255, a leading zero, a foreign byte inside the run: never accepted
+        if ((kind < 2 && p) || kind == 4 || kind == 5) CHECK(!acc);
+    }
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 2000;
     std::mt19937_64 rng(20261017);
@@ -619,14 +823,19 @@ int main(int argc, char** argv) {
     uint64_t dacc = 0, dref = 0;
     for (int it = 0; it < std::max(1, iters / 10); ++it) dparse_case(rng, &dacc, &dref);
     CHECK(dacc > 0 && dref > 0);
+    uint64_t wacc = 0, wref = 0;
+    for (int it = 0; it < std::max(3, iters / 40); ++it) dwave_case(rng, &wacc, &wref);
+    CHECK(wacc > 0 && wref > 0 && g_dwave_fast > 0);
     uint64_t sj = 0;
     for (int it = 0; it < std::max(1, iters / 10); ++it) sigjson_case(rng, &sj);
     CHECK(walked > (uint64_t)iters / 4);
     printf("kernel bodies ok: %llu chain cases (%llu resolved on the device path), %llu zstd blocks, %llu stream "
            "replicas, %llu repeat offsets, %llu signature JSON entries, %llu/%llu mutated texts accepted/refused, "
-           "%llu/%llu mutated Delta texts accepted/refused\n",
+           "%llu/%llu mutated Delta texts accepted/refused, %llu/%llu changed literal runs accepted/refused (%llu "
+           "parses in wave form, %llu chunks on the fast path)\n",
            (unsigned long long)cases, (unsigned long long)walked, (unsigned long long)blocks,
            (unsigned long long)replica, (unsigned long long)reps, (unsigned long long)sj, (unsigned long long)acc,
-           (unsigned long long)ref, (unsigned long long)dacc, (unsigned long long)dref);
+           (unsigned long long)ref, (unsigned long long)dacc, (unsigned long long)dref, (unsigned long long)wacc,
+           (unsigned long long)wref, (unsigned long long)g_dwave_runs, (unsigned long long)g_dwave_fast);
     return 0;
 }

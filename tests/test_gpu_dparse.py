@@ -13,7 +13,6 @@ Marked late (green on hardware since round 3). The CPU suite also runs the
 same chunk bodies on the emulated device and under ASan/UBSan
 (tests/csrc/emulated_checks.py, kernel_bodies_fuzz.cpp)."""
 import ctypes
-import json
 import random
 
 import numpy as np
@@ -24,9 +23,7 @@ from sy_amd import wire
 pytestmark = [pytest.mark.gpu, pytest.mark.late, pytest.mark.firstrun]
 
 
-def _compact(ops, ss, bs) -> bytes:
-    return json.dumps({"ops": [{"Copy": {"offset": o[1], "size": o[2]}} if o[0] == "C" else {"Data": list(o[1])}
-                               for o in ops], "source_size": ss, "block_size": bs}, separators=(",", ":")).encode()
+from delta_json_ref import compact as _compact  # noqa: E402  (json.dumps with serde's separators and field order)
 
 
 def _cases():

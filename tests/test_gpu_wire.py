@@ -109,3 +109,127 @@ def test_device_json_text_past_4gib(gpu):
     end = bytes(text[-(copy + tail_data + tail + 7):].cpu().numpy())
     assert end == (b'200,7]},{"Copy":{"offset":12345,"size":4096}},{"Data":[200,200,200,200,7]}'
                    + b'],"source_size":%d,"block_size":4096}' % (L + 4096))
+
+
+# ---------------------------------------------------------------------------
+# k_json_write's staging: the scan over 256 threads, the 4 * 4096 + 32 byte LDS text, the
+# 16-byte stores phased on the destination address; k_json_len's and k_json_write's
+# unaligned literal loads.  Each text against delta_json_ref.compact (json.dumps) and the
+# host writer, then back through the device parser (K7d) to the ops and literals.
+# ---------------------------------------------------------------------------
+from delta_json_ref import compact  # noqa: E402
+
+
+def _ops_of(kind, a, b, lit: bytes):
+    return [("C", x, y) if k == 0 else ("D", lit[x:x + y]) for k, x, y in zip(kind, a, b)]
+
+
+def _check_text(kind, a, b, ss, bs, lit: bytes, d_lit=None):
+    """Device text == compact == host text; the device parser reads it back.  Returns the text."""
+    import torch
+
+    ops = _ops_of(kind, a, b, lit)
+    ref = compact(ops, ss, bs)
+    assert wire.delta_to_json(kind, a, b, ss, bs, lit) == ref
+    if d_lit is None:
+        d_lit = torch.frombuffer(bytearray(lit) or bytearray(1), dtype=torch.uint8).cuda()[:len(lit)]
+    dev = wire.delta_to_json_device(kind, a, b, ss, bs, d_lit)
+    torch.cuda.synchronize()
+    got = dev.cpu().numpy().tobytes()
+    assert len(got) == len(ref)
+    assert got == ref
+    dops, dl, dss, dbs = wire.delta_from_json_device(dev)
+    back = dl.cpu().numpy().tobytes()
+    assert ([("C", x, y) if k == 0 else ("D", back[x:x + y]) for k, x, y in dops], dss, dbs) == (ops, ss, bs)
+    return ref
+
+
+def _mixed_small():
+    rng = random.Random(12)
+    lit = rng.randbytes(30000)
+    kind, a, b, pos = [], [], [], 0
+    for n in (0, 1, 5000, 4096, 0, 4097, 17, 8192, 3):
+        kind += [0, 1]
+        a += [rng.randrange(1 << rng.choice((4, 30, 63))), pos]
+        b += [4096, n]
+        pos += n
+    return kind, a, b, lit
+
+
+def test_device_json_destination_alignment(gpu):
+    """d_out at offsets 1, 3, 8, 15 from a 16-byte boundary with out_cap == len exactly:
+    the text, and every byte around it unchanged; with out_cap == len - 1 nothing is
+    written and *out_len is still len."""
+    import ctypes
+
+    import torch
+
+    from sy_amd._lib import check, lib
+
+    kind, a, b, lit = _mixed_small()
+    ref = _check_text(kind, a, b, len(lit), 4096, lit)
+    d_lit = torch.frombuffer(bytearray(lit), dtype=torch.uint8).cuda()
+    h = wire._delta_handle(kind, a, b, len(lit), 4096)
+    try:
+        got = ctypes.c_uint64()
+        for shift in (1, 3, 8, 15):
+            for cap in (len(ref), len(ref) - 1):
+                out = torch.full((len(ref) + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+                assert out.data_ptr() % 16 == 0
+                check(lib.sydelta_delta_to_json_device(h, d_lit.data_ptr(), d_lit.numel(), out.data_ptr() + 16 + shift,
+                                                       cap, ctypes.byref(got), None))
+                torch.cuda.synchronize()
+                o = out.cpu().numpy()
+                assert got.value == len(ref), (shift, cap)
+                if cap == len(ref):
+                    assert o[16 + shift:16 + shift + len(ref)].tobytes() == ref, shift
+                    assert (o[:16 + shift] == 0xEE).all() and (o[16 + shift + len(ref):] == 0xEE).all(), shift
+                else:
+                    assert (o == 0xEE).all(), shift
+    finally:
+        lib.sydelta_delta_free(h)
+
+
+@pytest.mark.parametrize("value,n", [(255, 4096), (0, 4096), (255, 4097), (0, 4097), (255, 8192), (0, 8192),
+                                     (255, 12288), (0, 12288)])
+def test_device_json_full_chunk_on_every_destination_phase(value, n, gpu):
+    """A Data op of n equal bytes as a non-first op, in pieces of 4096 bytes: one piece that
+    carries Sep, First and Last (4096; all-255: 16410 of the 16416 staged bytes at phase
+    15; all-0: the shortest text), a Last piece of 1 byte (4097), a full First and a full
+    Last piece (8192), a middle piece with neither (12288).  The digits of the Copy before
+    the op put its first piece on each destination phase 0..15."""
+    lit = bytes([value]) * n + b"\x07"
+    phases = set()
+    for digits in range(1, 17):
+        kind, a, b = [0, 1, 1], [10 ** (digits - 1), 0, n], [1, n, 1]
+        ref = _check_text(kind, a, b, n + 1, 4096, lit)
+        phases.add(ref.index(b',{"Data"') % 16)
+    assert phases == set(range(16))
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_device_json_digit_class_changes_at_thread_and_wave_boundaries(shift, gpu):
+    """1-, 2- and 3-digit values changing exactly every 16 bytes (a thread's share, and so
+    at every 1024-byte wave boundary too), and the same pattern one byte later."""
+    pat = []
+    for k in range(3 * 4096 // 16):
+        pat += [(9, 10, 99, 100, 255, 0, 200, 7)[k % 8]] * 16
+    lit = bytes([5] * shift + pat)
+    _check_text([1, 0, 1], [0, 1, 4096 + shift], [4096 + shift, 1, len(lit) - 4096 - shift], len(lit), 4096, lit)
+
+
+@pytest.mark.parametrize("view", [1, 2, 3])
+def test_device_json_literal_base_off_alignment(view, gpu):
+    """The literal tensor viewed at offsets 1, 2, 3 with Data ops whose source offsets are
+    multiples of 16: the base, not the op, sends k_json_len and k_json_write down their
+    unaligned loads."""
+    import torch
+
+    rng = random.Random(50 + view)
+    lit = rng.randbytes(3 * 4096 + 160)
+    whole = torch.frombuffer(bytearray(b"\xEE" * view + lit + b"\xEE" * 16), dtype=torch.uint8).cuda()
+    assert whole.data_ptr() % 16 == 0
+    d_lit = whole[view:view + len(lit)]
+    kind, a, b = [1, 0, 1, 1, 1], [0, 99, 4096 + 64, 2 * 4096 + 64, 3 * 4096 + 96], [4096 + 64, 4096, 4096, 4096 + 32, 64]
+    assert all(x % 16 == 0 for k, x in zip(kind, a) if k == 1)
+    _check_text(kind, a, b, len(lit), 4096, lit, d_lit)

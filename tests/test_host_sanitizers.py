@@ -102,7 +102,10 @@ def test_host_pool_under_tsan():
 def test_kernel_bodies_under_asan_ubsan():
     """K5b's chain bodies on 2000 random classified sources (marking threads shuffled)
     against walk_src, and K7z's block coder plus a thread-by-thread replica of its
-    parallel bit scatter on random texts, all under ASan + UBSan."""
+    parallel bit scatter on random texts, the JSON writers' and parsers' bodies, and the
+    wave form of the Delta JSON parse kernels (tests/csrc/dparse_wave.hpp: staged rows, SWAR
+    fast path, literal slab and its dword stores) against the plain chunk bodies, all under
+    ASan + UBSan."""
     if shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime.h"):
         pytest.skip("needs g++ and the HIP headers")
     os.makedirs(OUT, exist_ok=True)
