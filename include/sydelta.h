@@ -398,6 +398,60 @@ int sydelta_delta_to_json(const sydelta_delta *d, const uint8_t *lit, uint64_t l
  * d_lit and d_out may have any alignment. */
 int sydelta_delta_to_json_device(const sydelta_delta *d, const uint8_t *d_lit, uint64_t lit_len, uint8_t *d_out,
                                  uint64_t out_cap, uint64_t *out_len, void *stream);
+/* serde_json::to_string(&Delta) (ssh.rs:1003) for nfiles deltas in one call: the sender's
+ * wire text of a whole batch, between sydelta_delta_pairs_device and the compressor.
+ * File f: its text is byte for byte what sydelta_delta_to_json writes for deltas[f], its Data
+ *         ops reading d_lit[lit_off[f] + op.a, +op.b), op.a+op.b <= lit_len[f]; it goes to
+ *         d_out[text_off[f], +text_len[f]).
+ *  - Inputs: lit_off, lit_len, text_off and text_len are host arrays of nfiles entries.
+ *    deltas[f] may come from sydelta_delta_batch_get / sydelta_delta_batch_ptrs,
+ *    sydelta_delta_from_ops or sydelta_match_device; the same pointer may appear more than
+ *    once.  For a batch from sydelta_delta_pairs_device or sydelta_match_batch_device,
+ *    lit_off = src_off and lit_len = src_len, as in the batched apply.
+ *  - Text: ops are never merged (consecutive Copies stay separate ops, SURVEY rule R9); a
+ *    Data op with b == 0 is {"Data":[]}; a delta without ops is
+ *    {"ops":[],"source_size":N,"block_size":B}.
+ *  - Packing: the texts are packed in file order, text_off[f] = the sum over g < f of
+ *    text_len[g] rounded up to 16, so every text starts on a multiple of 16 from d_out (with
+ *    a 16-byte aligned d_out each text can go straight into sydelta_zstd_compress_device);
+ *    *out_need = text_off[nfiles-1] + text_len[nfiles-1].
+ *  - Lengths and writing: text_off, text_len and *out_need are always reported (computed on
+ *    the device from the literal bytes).  The texts are written only when d_out != NULL and
+ *    out_buf_len >= *out_need; otherwise no byte is written and the call still returns
+ *    SYDELTA_OK (the single-file call's convention).  sydelta_delta_batch_to_json_bound
+ *    gives an arena size that always suffices, so one call does.
+ *  - Writing: nothing outside [text_off[f], text_off[f] + text_len[f]); the pad bytes between
+ *    texts are not touched.  d_out and d_lit may have any alignment: 16-byte stores are
+ *    phased on the absolute destination address and the partial granules at a text's two
+ *    ends are written byte by byte.
+ *  - Reading: nothing outside file f's literal range, beyond the 16-byte granules holding its
+ *    first and last byte (Conventions, "Data layout in HBM").
+ *  - Validation: every table entry and every op of every file is validated on the host,
+ *    overflow-checked, before anything is queued; on an error nothing is written and the
+ *    message names the file and the op ("file F: op I: ...").  A Data op outside
+ *    [0, lit_len[f]), a literal range that leaves the arena (lit_off[f] + lit_len[f] >
+ *    lit_buf_len), an unknown op kind, a NULL deltas[f] or a NULL table with nfiles > 0:
+ *    SYDELTA_E_INVAL.
+ *  - nfiles == 0 returns SYDELTA_OK with *out_need = 0 without touching a device.
+ *  - Stream order: the work is ordered on `stream` (NULL: the thread's library stream) and
+ *    the texts are complete when the call returns.  The call waits for the stream once, at
+ *    its end (whether the arena holds the texts is decided on the device), and for an upload
+ *    slot only when the batch needs more table slices than the ring holds (never once per
+ *    file).  The number of launches depends on the number of table slices, never on nfiles;
+ *    heads and tails are written by the kernel.
+ *  - Staging: the tile and pair tables reach the device through a per-thread ring of
+ *    fixed-size pinned slices (8 x 1 MiB, whatever the batch; released when the thread
+ *    exits); their device copy and the scratch come from the library's stream-ordered pool
+ *    and return to it in stream order. */
+int sydelta_delta_batch_to_json_device(int device,
+        const sydelta_delta *const *deltas, uint64_t nfiles,
+        const uint8_t *d_lit, uint64_t lit_buf_len, const uint64_t *lit_off, const uint64_t *lit_len,
+        uint8_t *d_out, uint64_t out_buf_len,
+        uint64_t *text_off /* nfiles, written */, uint64_t *text_len /* nfiles, written */,
+        uint64_t *out_need, void *stream);
+/* Upper bound of *out_need above, from the ops alone (host only, no device): UINT64_MAX on a
+ * NULL entry or overflow. */
+uint64_t sydelta_delta_batch_to_json_bound(const sydelta_delta *const *deltas, uint64_t nfiles);
 /* serde_json::to_string(&Vec<BlockChecksum>) of a signature in HBM, written on the device:
  * the line `sy-remote checksums` prints (sy-remote.rs:146-147) and ssh.rs:967-973 parses,
  * for the SoA sydelta_signature_device writes (n blocks in index order, block i at offset

@@ -92,6 +92,69 @@ def delta_to_json_device(kind, a, b, source_size: int, block_size: int, d_lit, s
         lib.sydelta_delta_free(h)
 
 
+def delta_batch_to_json_device(deltas, lit, loffs, llens, out=None, stream=None):
+    """The Delta texts of a whole batch written on the device in one call
+    (sydelta_delta_batch_to_json_device): file f's text is delta_to_json's of deltas[f], its
+    Data ops reading lit[loffs[f] + op.a, +op.b) (for a batched match's deltas: the sources'
+    offsets and lengths).  `deltas` is a DeltaBatch or a list of DeviceDelta.  The texts are
+    packed into `out` in file order, each starting on a multiple of 16; with out=None an arena
+    of sydelta_delta_batch_to_json_bound bytes is allocated, so one call does.
+    Returns (out trimmed to the packed size, toffs, tlens) with file f's text at
+    out[toffs[f] : toffs[f] + tlens[f]].  Raises SyDeltaError (SYDELTA_E_INVAL) when a given
+    `out` does not hold the texts: nothing was written."""
+    import torch
+
+    from .device import _OP_DTYPE as _DEV_OP_DTYPE
+    from .device import DeltaBatch, _ptr, _stream
+
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (loffs, llens)]
+    own = []
+    if isinstance(deltas, DeltaBatch):
+        n = deltas.count
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        if int(lib.sydelta_delta_batch_ptrs(deltas.h, ptrs, n)) != n:
+            raise ValueError("delta batch changed size")
+    else:
+        n = len(deltas)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        for f, d in enumerate(deltas):
+            if d.handle is not None:  # the library's own delta: no copy of the ops
+                ptrs[f] = d.handle.h if isinstance(d.handle.h, int) else d.handle.h.value
+                continue
+            k = len(d.kind)
+            ops = np.zeros(k, dtype=_DEV_OP_DTYPE)
+            if k:
+                ops["kind"], ops["a"], ops["b"] = d.kind, d.a, d.b
+            h = lib.sydelta_delta_from_ops(ops.ctypes.data if k else None, k, d.source_size, d.block_size)
+            if not h:
+                for o in own:
+                    lib.sydelta_delta_free(o)
+                raise ValueError(f"file {f}: bad op array")
+            own.append(h)
+            ptrs[f] = h
+    try:
+        if any(len(a) != n for a in arrs):
+            raise ValueError("offset / length tables and deltas differ in length")
+        if out is None:
+            bound = int(lib.sydelta_delta_batch_to_json_bound(ptrs, n))
+            if bound == 0xFFFFFFFFFFFFFFFF:
+                raise ValueError("no bound for the batch's text (a NULL delta or a size that overflows)")
+            out = torch.empty(max(bound, 1), dtype=torch.uint8, device=lit.device)
+        toffs = np.zeros(n, dtype=np.uint64)
+        tlens = np.zeros(n, dtype=np.uint64)
+        need = ctypes.c_uint64()
+        check(lib.sydelta_delta_batch_to_json_device(
+            lit.device.index or 0, ptrs, n, _ptr(lit) if lit.numel() else None, lit.numel(), arrs[0].ctypes.data,
+            arrs[1].ctypes.data, _ptr(out), out.numel(), toffs.ctypes.data, tlens.ctypes.data, ctypes.byref(need),
+            _stream(stream)))
+        if need.value > out.numel():
+            raise _lib.SyDeltaError(_lib.SYDELTA_E_INVAL, f"the batch's text needs {need.value} bytes, out holds {out.numel()}")
+    finally:
+        for o in own:
+            lib.sydelta_delta_free(o)
+    return out[:need.value], toffs, tlens
+
+
 def checksums_to_json_device(d_weak, d_strong, block_size: int, last_size: int, stream=None):
     """serde_json::to_string(&Vec<BlockChecksum>) of a signature in HBM (the weak/strong
     tensors of device.signature), written on the device (sy-remote.rs:146-147); returns
