@@ -492,6 +492,56 @@ int sydelta_delta_from_json_device(const uint8_t *d_text, uint64_t len, uint8_t 
 uint64_t sydelta_zstd_bound(uint64_t len);
 int sydelta_zstd_compress_device(int device, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t out_cap,
                                  uint64_t *out_len, void *stream);
+/* compress(delta_json, Compression::Zstd) (ssh.rs:1009-1017) for nfiles texts in one call: the
+ * sender's wire bytes of a whole batch, behind sydelta_delta_batch_to_json_device.
+ * File f: its frame is byte for byte what sydelta_zstd_compress_device writes for the text
+ *         d_in[text_off[f], +text_len[f]) alone (an empty text: the 17-byte frame of one empty
+ *         Raw block); it goes to d_out[frame_off[f], +frame_len[f]).
+ *  - Inputs: text_off, text_len, frame_off and frame_len are host arrays of nfiles entries.
+ *    d_in and every text_off[f] are multiples of 16, and every text lies inside in_buf_len:
+ *    exactly the arena and tables sydelta_delta_batch_to_json_device returns.  Texts may
+ *    overlap or repeat.
+ *  - Packing: the frames sit back to back in file order, without padding (they are wire
+ *    bytes; a decoder takes any alignment): frame_off[f] = the sum over g < f of
+ *    frame_len[g]; *out_need = their total.
+ *  - Bound: sydelta_zstd_batch_bound = the sum of sydelta_zstd_bound(text_len[f]) (host only,
+ *    no device); UINT64_MAX on overflow or a NULL table with nfiles > 0.  An arena of that
+ *    size always suffices, so one call does.
+ *  - Arena too small: frame_off, frame_len and *out_need are always reported (computed on the
+ *    device).  With out_buf_len < *out_need the call returns SYDELTA_E_INVAL ("arena holds X,
+ *    the batch needs Y"): nothing outside [0, out_buf_len) has been written, what lies inside
+ *    is unspecified.  d_out == NULL with out_buf_len == 0 is the size query: SYDELTA_OK,
+ *    nothing written.
+ *  - Writing: nothing outside [0, *out_need) of d_out; d_out may have any alignment.
+ *  - Reading: nothing outside the texts, beyond the 16-byte granule holding a text's last byte
+ *    (Conventions, "Data layout in HBM").
+ *  - Validation: every table entry is validated on the host, overflow-checked, before anything
+ *    is queued; the message names the file ("file F: ...").  A d_in or a text_off[f] that is
+ *    no multiple of 16, a text that leaves the arena (text_off[f] + text_len[f] >
+ *    in_buf_len), a NULL table with nfiles > 0, a NULL d_out with out_buf_len > 0 or a NULL
+ *    out_need: SYDELTA_E_INVAL.
+ *  - nfiles == 0 returns SYDELTA_OK with *out_need = 0 without touching a device.
+ *  - Stream order: the work is ordered on `stream` (NULL: the thread's library stream) and
+ *    the frames are complete when the call returns.  The blocks (128 KiB of a text, or one
+ *    empty text) go through in rounds of at most 4096 (SYDELTA_ZSTD_BATCH sets another count,
+ *    read per call; halved down to 64 on a device short of memory); a round's placement comes
+ *    from a scan on top of a base kept on the device, so the host reads nothing between
+ *    rounds and the call waits for the stream once, at its end (and for an upload slot only
+ *    past 65 536 files).  The number of launches depends on the number of rounds, never on
+ *    nfiles.  Rounds ignore file boundaries.
+ *  - After the wait every frame_len[f] is checked against 17 <= frame_len[f] <=
+ *    sydelta_zstd_bound(text_len[f]); a violation is SYDELTA_E_KERNEL.
+ *  - Staging: the file table reaches the device through two per-thread pinned slots of
+ *    768 KiB (whatever the batch; released when the thread exits); its device copy and the
+ *    round's scratch (about 1.6 MiB per block) are one allocation from the library's
+ *    stream-ordered pool and return to it in stream order. */
+int sydelta_zstd_compress_batch_device(int device,
+        const uint8_t *d_in, uint64_t in_buf_len, const uint64_t *text_off, const uint64_t *text_len,
+        uint64_t nfiles,
+        uint8_t *d_out, uint64_t out_buf_len,
+        uint64_t *frame_off /* nfiles, written */, uint64_t *frame_len /* nfiles, written */,
+        uint64_t *out_need, void *stream);
+uint64_t sydelta_zstd_batch_bound(const uint64_t *text_len, uint64_t nfiles);
 /* The inverse, for any writer's frames (sy-remote.rs:160-166: compress::decompress of a
  * payload that starts with the zstd magic): d_in[0, len) holds exactly one zstd frame
  * (RFC 8878: Raw / RLE / Compressed blocks, Huffman literals in 1 or 4 streams with direct

@@ -19,6 +19,7 @@
 // Launch wrappers at the bottom are the only symbols the host API uses.
 #include "sydelta_device.hpp"
 #include "sydelta_internal.hpp"
+#include "sydelta_zstdbatch.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -2663,13 +2664,20 @@ __device__ __forceinline__ bool z_has_brace(uint32_t w) {
     return ((x - 0x01010101u) & ~x & 0x80808080u) != 0;
 }
 // zstd::gap_count from the text in global memory (L1/L2: the 255 bytes behind p), four
-// bytes a load; the first 259 positions byte by byte.
+// bytes a load; the first 259 positions byte by byte.  Every count is an LDS atomic: the
+// lanes of a wave step through the distances together, and two '{' of the first 259 bytes
+// at the same distance from an earlier one (a Copy op's text every 44 bytes) would lose a
+// count to zstd::gap_count's plain ++ and with it a tie between two candidate distances.
 __device__ __forceinline__ void z_gap_count(const uint8_t* __restrict__ in, uint32_t p, uint32_t* gaps) {
+    uint32_t seen = 0;
     if (p < 259) {
-        zstd::gap_count(in, p, gaps);
+        for (uint32_t d = 1; d < 256 && d <= p && seen < 3; ++d)
+            if (in[p - d] == '{') {
+                atomicAdd(&gaps[d], 1u);
+                ++seen;
+            }
         return;
     }
-    uint32_t seen = 0;
     for (uint32_t d0 = 1; d0 < 256 && seen < 3; d0 += 4) {
         const uint32_t w = zstd::ld32u(in + p - d0 - 3);  // byte 3 is at p - d0
         if (!z_has_brace(w)) continue;
@@ -3324,19 +3332,18 @@ __device__ __forceinline__ uint32_t z_lz_content(ZLds& L, const uint8_t* __restr
 }
 
 
-__global__ __launch_bounds__(kZT) void k_zstd_block(const uint8_t* __restrict__ text, uint64_t len, uint64_t b0,
-                                                    uint8_t* __restrict__ slots, uint8_t* __restrict__ lz, uint64_t nlz,
-                                                    uint32_t* __restrict__ size_out, uint32_t* __restrict__ type_out,
-                                                    uint64_t* __restrict__ len64, uint32_t timing) {
-    __shared__ ZLds L;
+// The one block coder, a workgroup of kZT threads: the content of in[0, n) (16-byte aligned,
+// readable to the end of its last granule; n == 0 is an empty Raw block) into `slot` with the
+// scratch `sc`.  Thread 0 stores the block's type, its size and its placed length: 3 + size
+// behind `head` bytes of frame header.  k_zstd_block (a text's blocks) and k_zstdb_block (a
+// batch's) both call it, so their frames are the same bytes.  (No __restrict__ here: what
+// the kernels' arguments promise reaches the body through `in`, `slot` and `sc`.)
+__device__ __forceinline__ void z_block(ZLds& L, const uint8_t* in, const uint32_t n, uint8_t* slot,
+                                        const zstd::SeqScratch sc, const uint32_t timing, uint32_t* type_out,
+                                        uint32_t* size_out, uint64_t* len64, const uint32_t head) {
     uint64_t tph = timing ? wall_clock64() : 0;
     auto phase = [&](int k) { z_phase(timing, tph, k); };
     const uint32_t tid = threadIdx.x, wid = tid >> 6;
-    const uint64_t gb = b0 + blockIdx.x;
-    const uint8_t* in = text + gb * zstd::kBlockMax;
-    const uint32_t n = (uint32_t)min<uint64_t>(zstd::kBlockMax, len - gb * zstd::kBlockMax);
-    uint8_t* slot = slots + (uint64_t)blockIdx.x * zstd::kBlockMax;
-    const zstd::SeqScratch sc = zstd::seq_scratch_at(lz, nlz, blockIdx.x);
     for (uint32_t i = tid; i < 4 * 256; i += kZT) (&L.hist[0][0])[i] = 0;
     for (uint32_t i = tid; i < 256; i += kZT) {
         L.gaps[i] = 0;
@@ -3511,10 +3518,40 @@ __global__ __launch_bounds__(kZT) void k_zstd_block(const uint8_t* __restrict__ 
             t = 2;
             size = L.state[3];
         }
-        type_out[blockIdx.x] = t;
-        size_out[blockIdx.x] = size;
-        len64[blockIdx.x] = 3ull + size;
+        *type_out = t;
+        *size_out = size;
+        *len64 = head + 3ull + size;
     }
+}
+
+__global__ __launch_bounds__(kZT) void k_zstd_block(const uint8_t* __restrict__ text, uint64_t len, uint64_t b0,
+                                                    uint8_t* __restrict__ slots, uint8_t* __restrict__ lz, uint64_t nlz,
+                                                    uint32_t* __restrict__ size_out, uint32_t* __restrict__ type_out,
+                                                    uint64_t* __restrict__ len64, uint32_t timing) {
+    __shared__ ZLds L;
+    const uint64_t gb = b0 + blockIdx.x;
+    const uint8_t* in = text + gb * zstd::kBlockMax;
+    const uint32_t n = (uint32_t)min<uint64_t>(zstd::kBlockMax, len - gb * zstd::kBlockMax);
+    uint8_t* slot = slots + (uint64_t)blockIdx.x * zstd::kBlockMax;
+    const zstd::SeqScratch sc = zstd::seq_scratch_at(lz, nlz, blockIdx.x);
+    z_block(L, in, n, slot, sc, timing, type_out + blockIdx.x, size_out + blockIdx.x, len64 + blockIdx.x, 0u);
+}
+
+// A batch's blocks [b0, b0 + gridDim.x) (sydelta_zstdbatch.hpp): workgroup i finds block
+// b0 + i's file by bisection and codes it as k_zstd_block would; len64 also counts the frame
+// header in front of a file's first block.
+__global__ __launch_bounds__(kZT) void k_zstdb_block(const uint8_t* __restrict__ arena,
+                                                     const zstdb::File* __restrict__ files, uint64_t nfiles, uint64_t b0,
+                                                     uint8_t* __restrict__ slots, uint8_t* __restrict__ lz, uint64_t nlz,
+                                                     uint32_t* __restrict__ size_out, uint32_t* __restrict__ type_out,
+                                                     uint64_t* __restrict__ len64, uint32_t timing) {
+    __shared__ ZLds L;
+    const zstdb::Block B = zstdb::block_at(files, nfiles, b0 + blockIdx.x);
+    uint8_t* slot = slots + (uint64_t)blockIdx.x * zstd::kBlockMax;
+    const zstd::SeqScratch sc = zstd::seq_scratch_at(lz, nlz, blockIdx.x);
+    static_assert(zstdb::placed_len(true, 7) == zstd::kFrameHeader + 3 + 7, "placed length: head + 3 + size");
+    z_block(L, arena + B.at, B.n, slot, sc, timing, type_out + blockIdx.x, size_out + blockIdx.x, len64 + blockIdx.x,
+            B.first ? zstd::kFrameHeader : 0u);
 }
 
 // Blocks [b0, b0 + nb) behind their headers at base + off[i]; block 0 of the frame also
@@ -4781,6 +4818,18 @@ hipError_t launch_zstd_blocks(const uint8_t* d_text, uint64_t len, uint64_t b0, 
     ProfScope ps(prof, s, "k_zstd_block");
     hipLaunchKernelGGL(k_zstd_block, dim3(nb), dim3(kZT), 0, s, d_text, len, b0, d_slots, d_lz, (uint64_t)nb, d_size,
                        d_type, d_len64, timing ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_zstdb_blocks(const uint8_t* d_in, const zstdb::File* d_files, uint64_t nfiles, uint64_t b0, uint32_t nb,
+                               uint8_t* d_slots, uint8_t* d_lz, uint32_t* d_size, uint32_t* d_type, uint64_t* d_len64,
+                               hipStream_t s, Profiler* prof) {
+    if (!nb) return hipSuccess;
+    if (!nfiles) return hipErrorInvalidValue;
+    static const bool timing = getenv("SYDELTA_PHASE_TIMING") != nullptr;
+    ProfScope ps(prof, s, "k_zstdb_block");
+    hipLaunchKernelGGL(k_zstdb_block, dim3(nb), dim3(kZT), 0, s, d_in, d_files, nfiles, b0, d_slots, d_lz, (uint64_t)nb,
+                       d_size, d_type, d_len64, timing ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -429,6 +429,17 @@ def apply_batch(basis: torch.Tensor, boffs, blens, deltas, lit: torch.Tensor, lo
     return out, ooffs, stats
 
 
+def delta_batch_to_wire(deltas, lit: torch.Tensor, loffs, llens, stream=None):
+    """The sender's wire bytes of a whole batch (ssh.rs:1003-1017), two calls for any number of
+    files: the Delta texts (wire.delta_batch_to_json_device), then their zstd frames
+    (wire.zstd_compress_batch_device).  `deltas`, `lit`, `loffs`, `llens` as for the first.
+    Returns (frames, foffs, flens): file f's payload is frames[foffs[f] : foffs[f] + flens[f]]."""
+    from . import wire
+
+    text, toffs, tlens = wire.delta_batch_to_json_device(deltas, lit, loffs, llens, stream=stream)
+    return wire.zstd_compress_batch_device(text, toffs, tlens, stream=stream)
+
+
 ZSTD_MAGIC = bytes([0x28, 0xB5, 0x2F, 0xFD])
 
 

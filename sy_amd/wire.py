@@ -237,6 +237,38 @@ def zstd_compress_device(d_text, stream=None, device: int | None = None):
     return out[:got.value]
 
 
+def zstd_compress_batch_device(text, toffs, tlens, out=None, stream=None):
+    """The zstd frames of a whole batch of texts in one call (sydelta_zstd_compress_batch_device):
+    file f's frame is zstd_compress_device's of text[toffs[f] : toffs[f] + tlens[f]].  `text`
+    is a uint8 device tensor that starts 16-byte aligned and every toffs[f] is a multiple of 16:
+    what delta_batch_to_json_device returns.  The frames are packed into `out` back to back in
+    file order; with out=None an arena of sydelta_zstd_batch_bound bytes is allocated, so one
+    call does.  Returns (out trimmed to the packed size, foffs, flens) with file f's frame at
+    out[foffs[f] : foffs[f] + flens[f]].  Raises SyDeltaError (SYDELTA_E_INVAL) when a given
+    `out` does not hold the frames."""
+    import torch
+
+    from .device import _ptr, _stream
+
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (toffs, tlens)]
+    n = len(arrs[0])
+    if len(arrs[1]) != n:
+        raise ValueError("offset and length tables differ in length")
+    if out is None:
+        bound = int(lib.sydelta_zstd_batch_bound(arrs[1].ctypes.data, n))
+        if bound == 0xFFFFFFFFFFFFFFFF:
+            raise ValueError("no bound for the batch's frames (the lengths overflow)")
+        out = torch.empty(max(bound, 1), dtype=torch.uint8, device=text.device)
+    foffs = np.zeros(n, dtype=np.uint64)
+    flens = np.zeros(n, dtype=np.uint64)
+    need = ctypes.c_uint64()
+    check(lib.sydelta_zstd_compress_batch_device(
+        text.device.index or 0, _ptr(text) if text.numel() else None, text.numel(), arrs[0].ctypes.data,
+        arrs[1].ctypes.data, n, _ptr(out), out.numel(), foffs.ctypes.data, flens.ctypes.data, ctypes.byref(need),
+        _stream(stream)))
+    return out[:need.value], foffs, flens
+
+
 def zstd_decompress_device(d_frame, stream=None, device: int | None = None, out=None):
     """The bytes of one zstd frame held in a uint8 device tensor, decoded on the device
     (sy-remote.rs:160-166: compress::decompress), as a uint8 device tensor: frames of any
