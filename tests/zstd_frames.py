@@ -39,7 +39,9 @@ def _z():
 def libzstd_path() -> str:
     """File of the loaded libzstd (the sanitizer program links it)."""
     for line in open("/proc/self/maps"):
-        if "libzstd" in line:
+        # the system library alone: test_zstd's host form is build/zstd_ref/libzstd_ref.so, and which
+        # of the two the kernel maps lower depends on what else the process has loaded
+        if "/libzstd.so" in line:
             return line.split()[-1]
     raise RuntimeError("libzstd is not loaded")
 
