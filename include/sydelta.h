@@ -555,6 +555,60 @@ uint64_t sydelta_zstd_batch_bound(const uint64_t *text_len, uint64_t nfiles);
  * Content_Checksum flag, 4 GiB or more of output, corrupt content. */
 int sydelta_zstd_decompress_device(int device, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t out_cap,
                                    uint64_t *out_len, void *stream);
+/* compress::decompress (sy-remote.rs:160-166) for nfiles frames in one call: the receiver's
+ * first step for the arena sydelta_zstd_compress_batch_device (or any sender) hands over.
+ * File f: d_in[frame_off[f], +frame_len[f]) holds exactly one zstd frame; its text is byte for
+ *         byte what sydelta_zstd_decompress_device writes for that frame alone, and goes to
+ *         d_out[text_off[f], +text_len[f]).  Every form and refusal of the single call holds
+ *         per file.  Files are independent: no table, repeat offset (1, 4, 8 at every file's
+ *         start) or match reaches from one file into another; an offset is checked against
+ *         its position inside its own text.
+ *  - Inputs: frame_off, frame_len, text_off, text_len and file_status are host arrays of
+ *    nfiles entries.  d_in, d_out and every frame_off[f] may have any alignment: exactly the
+ *    arena and tables sydelta_zstd_compress_batch_device returns.  Frames may overlap, repeat
+ *    or come in any order.
+ *  - Packing: the layout of sydelta_delta_batch_to_json_device: text_off[f] = the sum over
+ *    g < f of text_len[g] rounded up to 16; *out_need = text_off[nfiles-1] + text_len[nfiles-1].
+ *    Decoding what sydelta_zstd_compress_batch_device made of an arena returns that arena's
+ *    own tables.
+ *  - Lengths and writing: text_off, text_len and *out_need are always reported (computed on
+ *    the device).  The texts are written only when d_out != NULL and out_buf_len >= *out_need;
+ *    otherwise no byte is written and the call still returns SYDELTA_OK (size query).  Nothing
+ *    outside the texts is changed: the pad bytes between them and the bytes behind *out_need
+ *    keep their values.
+ *  - Refused frames, file_status == NULL: a batch with any refused frame returns
+ *    SYDELTA_E_INVAL with the message of the lowest such file, "file F: zstd frame: block B:
+ *    <reason>" (the single call's reasons); nothing is written.
+ *  - Refused frames, file_status != NULL: the call returns SYDELTA_OK; file_status[f] is 0 for
+ *    a decoded file, else the single call's status key (block << 32) | code.  A refused file
+ *    has text_len[f] = 0 and takes no room in the packing; every other file is decoded exactly
+ *    as if the refused ones were empty.  Decode the refused payloads on the host.
+ *    frame_len[f] < 4 is that file's "truncated frame", not a call error.
+ *  - Size limit: positions in the arena are 32-bit on the device, so a batch with *out_need >=
+ *    4 GiB is refused with SYDELTA_E_INVAL ("the batch regenerates X bytes; split it below
+ *    4 GiB"), before any scratch is sized from that sum and naming no file: split the batch.
+ *    A single file of 4 GiB or more is refused as in the single call, naming its file.
+ *  - Validation, on the host before a device is touched (SYDELTA_E_INVAL, the message names
+ *    the file where there is one): a NULL table with nfiles > 0, a NULL out_need, a NULL d_in
+ *    with a non-empty frame, a NULL d_out with out_buf_len > 0, a frame that leaves the arena
+ *    (frame_off[f] + frame_len[f] > in_buf_len, overflow-checked).
+ *  - nfiles == 0 returns SYDELTA_OK with *out_need = 0 without touching a device.
+ *  - Stream order: the work is ordered on `stream` (NULL: the thread's library stream) and
+ *    complete when the call returns.  The host waits three times whatever the batch: for the
+ *    per-file counts, for the sizes and statuses, and at the end.  The numbers of copies,
+ *    allocations and launches do not depend on nfiles (an upload slot more per 40 960 files).
+ *  - Staging: the file table and the files' bases reach the device through two per-thread
+ *    pinned slots of 640 KiB (whatever the batch; released when the thread exits); the scratch
+ *    (the shared block table, tables, literals, sequences, and four bytes per arena byte) comes
+ *    from the library's stream-ordered pool and returns to it in stream order.  A batch is not
+ *    split when memory is short: an allocation failure is SYDELTA_E_OOM with the byte count. */
+int sydelta_zstd_decompress_batch_device(int device,
+        const uint8_t *d_in, uint64_t in_buf_len, const uint64_t *frame_off, const uint64_t *frame_len,
+        uint64_t nfiles,
+        uint8_t *d_out, uint64_t out_buf_len,
+        uint64_t *text_off /* nfiles, written */, uint64_t *text_len /* nfiles, written */,
+        uint64_t *file_status /* nfiles, written; or NULL */,
+        uint64_t *out_need, void *stream);
 /* serde_json::from_str::<Delta> (sy-remote.rs:175): a host delta holding its literal
  * bytes, ready for sydelta_apply_delta. */
 int sydelta_delta_from_json(const char *json, uint64_t len, sydelta_delta **out);

@@ -129,6 +129,8 @@ SIGNATURES = [
     ("sydelta_zstd_compress_batch_device", _i, [_i, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp,
                                                 ctypes.POINTER(_u64), _vp]),
     ("sydelta_zstd_decompress_device", _i, [_i, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
+    ("sydelta_zstd_decompress_batch_device", _i, [_i, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp,
+                                                  ctypes.POINTER(_u64), _vp]),
     ("sydelta_block_compare_device", _i, [_i, _vp, _u64, _vp, _u64, _u64, _vp, _vp, ctypes.POINTER(BlockCompareStatsC)]),
     ("sydelta_estimate_change_ratio_device", _i, [_i, _vp, _u64, _vp, _u64, _u64, ctypes.c_int64, ctypes.c_double,
                                                   _vp, ctypes.POINTER(ChangeRatioC)]),
@@ -173,7 +175,7 @@ def _load() -> ctypes.CDLL:
             # decoder, the batched apply, the batched Delta JSON writer and the batched zstd
             # compressor live in translation units of their own (sydelta_blake3.cpp,
             # sydelta_unzstd_api.cpp, sydelta_applybatch.cpp, sydelta_jsonbatch.cpp,
-            # sydelta_zstdbatch.cpp); a library built from the
+            # sydelta_zstdbatch.cpp, sydelta_unzstdbatch.cpp); a library built from the
             # other host units alone (the emulated-device build of the host-logic tests, loaded
             # through this table from another path) has none of them, and calling one there
             # raises AttributeError.

@@ -440,6 +440,17 @@ def delta_batch_to_wire(deltas, lit: torch.Tensor, loffs, llens, stream=None):
     return wire.zstd_compress_batch_device(text, toffs, tlens, stream=stream)
 
 
+def wire_batch_to_text(frames: torch.Tensor, foffs, flens, out: torch.Tensor | None = None, refused_ok: bool = False,
+                       stream=None):
+    """The receiver's first step for a whole batch (sy-remote.rs:160-166), one call for any
+    number of files: delta_batch_to_wire's inverse up to the JSON
+    (wire.zstd_decompress_batch_device).  Returns (text, toffs, tlens), and the per-file status
+    with refused_ok: file f's Delta JSON is text[toffs[f] : toffs[f] + tlens[f]]."""
+    from . import wire
+
+    return wire.zstd_decompress_batch_device(frames, foffs, flens, out=out, refused_ok=refused_ok, stream=stream)
+
+
 ZSTD_MAGIC = bytes([0x28, 0xB5, 0x2F, 0xFD])
 
 

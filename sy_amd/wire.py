@@ -299,6 +299,54 @@ def zstd_decompress_device(d_frame, stream=None, device: int | None = None, out=
     return out[:n.value]
 
 
+def zstd_decompress_batch_device(frames, foffs, flens, out=None, refused_ok=False, stream=None):
+    """The texts of a whole batch of zstd frames in one call
+    (sydelta_zstd_decompress_batch_device): file f's frame is frames[foffs[f] : foffs[f] +
+    flens[f]] (a uint8 device tensor and tables of any alignment and order: what
+    zstd_compress_batch_device returns, or any sender's payloads), its text what
+    zstd_decompress_device returns for that frame alone.  The texts are packed into `out` in
+    file order, each at a multiple of 16 (delta_batch_to_json_device's layout).  With out=None
+    the sizes are asked for first and an arena of that size is allocated: the stages up to the
+    stitch (counts, scan, tables, entropy decode, stitch, offsets) run twice, so a caller that
+    knows a bound passes `out` for a single call.  Returns (text, toffs, tlens) with file f's
+    text at text[toffs[f] : toffs[f] + tlens[f]]; nothing else of `out` is changed.
+
+    A frame the device decoder refuses (see zstd_decompress_device) raises SyDeltaError
+    (SYDELTA_E_INVAL, "file F: zstd frame: block B: <reason>") and nothing is written.  With
+    refused_ok=True the call succeeds instead and returns (text, toffs, tlens, status):
+    status[f] is 0 for a decoded file, else (block << 32) | code; such a file has tlens[f] = 0
+    and takes no room, and its payload is for the host decoder.  A batch of 4 GiB or more of
+    text is refused: split it."""
+    import torch
+
+    from .device import _ptr, _stream
+
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (foffs, flens)]
+    n = len(arrs[0])
+    if len(arrs[1]) != n:
+        raise ValueError("offset and length tables differ in length")
+    toffs = np.zeros(n, dtype=np.uint64)
+    tlens = np.zeros(n, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint64) if refused_ok else None
+    need = ctypes.c_uint64()
+    fp = _ptr(frames) if frames.numel() else None
+
+    def call(o):
+        check(lib.sydelta_zstd_decompress_batch_device(
+            frames.device.index or 0, fp, frames.numel(), arrs[0].ctypes.data, arrs[1].ctypes.data, n,
+            _ptr(o) if o is not None and o.numel() else None, o.numel() if o is not None else 0, toffs.ctypes.data,
+            tlens.ctypes.data, status.ctypes.data if refused_ok else None, ctypes.byref(need), _stream(stream)))
+
+    if out is None:
+        call(None)
+        out = torch.empty(max(1, need.value), dtype=torch.uint8, device=frames.device)
+    call(out)
+    if need.value > out.numel():
+        raise _lib.SyDeltaError(_lib.SYDELTA_E_INVAL, f"the batch's text needs {need.value} bytes, out holds {out.numel()}")
+    res = (out[:need.value], toffs, tlens)
+    return res + (status,) if refused_ok else res
+
+
 def delta_from_json(text: bytes):
     """-> (ops as [("C", offset, size) | ("D", literal bytes)], source_size, block_size)."""
     h = ctypes.c_void_p()
