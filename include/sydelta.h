@@ -35,6 +35,22 @@
  *    reference's streaming generator diverges from its own in-memory one
  *    (SURVEY.md App. A R10); the streaming entry rejects such sizes with
  *    SYDELTA_E_INVAL, the in-memory entry follows generate_delta.
+ *  - Block sizes above 128 KiB (the ABI takes them, sy never asks for them):
+ *    - signature entries: any block_size.  Whole 64-byte stripes up to
+ *      35 931 136 bytes take the row kernels (32-bit sums per lane, provable at
+ *      byte 255 up to there; 64-bit row totals), everything else the wave
+ *      kernels, whose 64-bit position-weighted sum is provable at byte 255 up to
+ *      380 371 000 bytes (255 n (n + 1) / 2 < 2^64).  Checked against the
+ *      reference arithmetic at 2 245 696 / 2 245 760 / 16 843 008 / 16 843 072,
+ *      8 MiB, 35 931 136 and 35 931 200.
+ *    - match entries: the reference rolls in u32 with n * old, exact while
+ *      255 n < 2^32 (n <= 16 843 009); the device is bit-exact with it up to
+ *      there (checked at 2 245 760).  An index of one file built with
+ *      SYDELTA_SCAN_WIDE unset or not 0 scans any such window (k_scan_g); with
+ *      SYDELTA_SCAN_WIDE=0 windows above 8192 go to the per-thread scan, which
+ *      holds windows up to 433 024 bytes: larger ones are refused with
+ *      SYDELTA_E_INVAL before anything is launched.  (A batched match takes
+ *      block sizes up to 8192.)
  */
 #ifndef SYDELTA_H
 #define SYDELTA_H

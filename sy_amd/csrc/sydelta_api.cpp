@@ -580,7 +580,7 @@ extern "C" int sydelta_signature_batch_device(int device, const uint8_t* d_buf, 
     for (uint64_t f = 0; f < nfiles; ++f) fblk[f + 1] = fblk[f] + (len[f] + block_size - 1) / block_size;
     const uint64_t total = fblk[nfiles];
     if (!total) return SYDELTA_OK;
-    bool fast = block_size % 64 == 0 && block_size >= 256 && block_size <= (1ull << 31);
+    bool fast = block_size % 64 == 0 && block_size >= 256 && block_size <= kRowHashMaxN;
     for (uint64_t f = 0; f < nfiles && fast; ++f) fast = !len[f] || ((uintptr_t)(d_buf + off[f]) & 15) == 0;
     if (fast) {
         std::vector<uint64_t> t;
@@ -1584,6 +1584,18 @@ bool wide_scan(const sydelta_index* x) {
     return x->ix.l1 != nullptr && scan_wide_mode() != 0;
 }
 
+// Windows above scan_max_window() are scanned by k_scan_g when the index carries its level-1
+// filter (any window: its LDS and grid do not grow with it), else by the per-thread k_scan,
+// whose LDS prefix arrays do: refused here, before any launch, when they cannot fit.
+int check_scan_window(const sydelta_index* x) {
+    if (x->bs > scan_max_window() && !wide_scan(x) && x->bs > kScanThreadMaxN)
+        return fail(SYDELTA_E_INVAL,
+                    "block_size %llu: without the index's level-1 filter (one file, SYDELTA_SCAN_WIDE not 0) "
+                    "the scan holds windows up to %u",
+                    (unsigned long long)x->bs, kScanThreadMaxN);
+    return SYDELTA_OK;
+}
+
 int probe_mode_env() {
     const char* e = getenv("SYDELTA_PROBE");  // "0" never, "1" always, unset/other: auto
     if (e && e[0] == '0') return 0;
@@ -2133,6 +2145,7 @@ void merge_ranges(std::vector<std::array<uint64_t, 3>>& r, uint64_t gap_blocks) 
 int Classifier::classify(int mode) {
     static const bool host_timing = getenv("SYDELTA_HOST_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
+    if (int r = check_scan_window(ix)) return r;
     if (int r = probe(mode)) return r;
     const double t_probe = ms_since(t0);
     const uint64_t gap_blocks = std::max<uint64_t>(1, scan_tile_positions() / n);
@@ -3274,6 +3287,7 @@ extern "C" int sydelta_match_device(sydelta_index* idx, const uint8_t* d_src, ui
     if (idx->nfiles != 1) return fail(SYDELTA_E_INVAL, "index holds %llu files; use sydelta_match_batch_device",
                                       (unsigned long long)idx->nfiles);
     if (len && !d_src) return fail(SYDELTA_E_INVAL, "NULL source");
+    if (int r = check_scan_window(idx)) return r;
     SYDELTA_ENTER_DEVICE(idx->device);
     hipStream_t s = stream ? (hipStream_t)stream : thread_stream(idx->device);
     sydelta_delta_batch b;

@@ -21,6 +21,20 @@ namespace sydelta {
 hipError_t dev_malloc_async(void** p, size_t bytes, hipStream_t s);
 
 constexpr uint32_t kEmptyKey = 0xFFFFFFFFu;  // never a valid weak: A = weak & 0xFFFF <= 65520
+// Largest window of the row layout (row_hash, sydelta_kcommon.hpp): k_sig_fast, k_sig_fast_batch,
+// k_probe_rows and k_verify_w's row path; larger windows take the wave kernels, whose Adler sums
+// are 64-bit throughout.  A lane keeps its byte sum (asum) and its in-group weighted sum
+// (vsum = sum of byte * (offset mod 16)) in 32 bits until the end of the window.  A lane
+// reads at most four 16-byte groups of each of the ceil(bs / 1024) pieces, and a group of
+// 0xFF bytes adds 255 * (0 + 1 + ... + 15) = 30 600 to vsum, so
+//   vsum <= 4 * 30 600 * pieces = 122 400 * pieces <= 2^32 - 1  <=>  pieces <= 35 089
+// (122 400 * 35 089 = 4 294 893 600; one piece more is 4 295 016 000 > 2^32), and asum, at
+// most 4 * 16 * 255 = 16 320 per piece, is far below.  The position-weighted sum (bpos, 64-bit)
+// is at most 255 * bs * (bs + 16) / 2 < 2^58 over the whole row.  The row totals are 64-bit.
+constexpr uint32_t kRowHashMaxN = 35089u * 1024u;  // 35 931 136
+static_assert(122400ull * (kRowHashMaxN / 1024) < (1ull << 32) && 122400ull * (kRowHashMaxN / 1024 + 1) > (1ull << 32) &&
+                  kRowHashMaxN % 64 == 0,
+              "kRowHashMaxN is the last block size whose per-lane sums are provable at byte 255");
 constexpr uint64_t kLdsFilterKeys = 16384;   // index sizes whose Bloom filter (<= 32 KiB) the scan keeps in LDS
 constexpr uint32_t kLdsFilterWordsMax = 8192;
 // k_scan_g's small-index mode keeps one file filter per wave in LDS: up to 4096 words
@@ -157,6 +171,9 @@ uint64_t scan_tile_positions();  // positions per tile of the LDS-staged scan
 // instead of the register-fed k_scan_g (read when the index is built and per call)
 int scan_wide_mode();
 uint32_t scan_max_window();      // largest block size the LDS-staged scan handles
+// Largest block size the per-thread k_scan's LDS holds (checked against its layout beside
+// scan_lds_bytes, sydelta_kernels.hip); a constant so that the host code needs no symbol for it.
+constexpr uint32_t kScanThreadMaxN = 433024;
 // Scratch the LDS-staged scan needs: filter-pass queues, scan_queue_entries() uint2
 // entries (2 workgroups per CU on up to 256 CUs; launch_scan checks; with no queues
 // given it takes them from its scratch).

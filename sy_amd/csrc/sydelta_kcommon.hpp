@@ -12,7 +12,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // no cross-row traffic.  Lane (slot, q) of a row takes stripes slot, slot+4,
 // slot+8, slot+12 of each piece (accumulator pair q): a load instruction reads
 // 256 contiguous bytes per row.  The next piece's loads are issued before the
-// current piece is hashed.  bs % 64 == 0, bs >= 256, blocks 16-byte aligned.
+// current piece is hashed.  bs % 64 == 0, 256 <= bs <= kRowHashMaxN, blocks 16-byte aligned.
 struct RowPiece {
     uint4 v[4];
 };
@@ -124,20 +124,19 @@ __device__ __forceinline__ void row_hash(const uint8_t* __restrict__ base, uint3
     }
     uint64_t f = fold64(acc_lo ^ c_tab.merge[2 * q], acc_hi ^ c_tab.merge[2 * q + 1]);
     f = sum_quad64(f);
-    // row sums of the Adler partials (16 lanes)
-    asum += dpp32<kDppQuadXor1>(asum);
-    asum += dpp32<kDppQuadXor2>(asum);
-    asum += dpp32<kDppRowRor4>(asum);
-    asum += dpp32<kDppRowRor8>(asum);
-    vsum += dpp32<kDppQuadXor1>(vsum);
-    vsum += dpp32<kDppQuadXor2>(vsum);
-    vsum += dpp32<kDppRowRor4>(vsum);
-    vsum += dpp32<kDppRowRor8>(vsum);
+    // row sums of the Adler partials (16 lanes), in 64 bits: a lane's asum and vsum fit 32
+    // bits up to kRowHashMaxN, the row's do not (on 0xFF bytes the row's vsum passes 2^32 at
+    // bs = 2 245 760 and its asum at 16 843 072, and 2^32 = 225 mod kMod).  vsum leaves
+    // through bpos: every term (bs - off) * s of a lane covers its j * byte, j < 16 <= bs - off.
+    bpos -= vsum;
     bpos = sum_quad64(bpos);
     bpos = dpp_add64<kDppRowRor4>(bpos);
     bpos = dpp_add64<kDppRowRor8>(bpos);
-    const uint32_t A = (1u + asum) % kMod;
-    const uint32_t B = (uint32_t)(((uint64_t)bs + bpos - vsum) % kMod);
+    uint64_t arow = sum_quad64((uint64_t)asum);
+    arow = dpp_add64<kDppRowRor4>(arow);
+    arow = dpp_add64<kDppRowRor8>(arow);
+    const uint32_t A = (uint32_t)((1u + arow) % kMod);
+    const uint32_t B = (uint32_t)(((uint64_t)bs + bpos) % kMod);
     weak_out = (B << 16) | A;
     strong_out = xxh3_aval((uint64_t)bs * P64_1 + f);
 }

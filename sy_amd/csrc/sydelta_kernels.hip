@@ -2471,7 +2471,7 @@ __global__ __launch_bounds__(256) void k_verify_w(ScanArgs a) {
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
     WaveOut wo = wave_out(a, wave);
-    const bool rows = a.n % 64 == 0 && a.n >= 256;  // row_hash: the long path, whole stripes
+    const bool rows = a.n % 64 == 0 && a.n >= 256 && a.n <= kRowHashMaxN;  // row_hash: the long path, whole stripes
     const uint32_t per = rows ? 4u : 1u;
     for (uint64_t r0 = wave * per; r0 < total; r0 += nwaves * per) {  // wave-uniform
         const uint64_t ri = rows ? r0 + row : r0;
@@ -4364,7 +4364,7 @@ hipError_t launch_signature(const uint8_t* d_buf, uint64_t len, uint64_t bs, uin
     const uint64_t nfull = len / bs;
     const bool aligned = (((uintptr_t)d_buf) & 15) == 0;
     uint64_t done = 0;
-    if (nfull && aligned && bs % 64 == 0 && bs >= 256 && bs <= (1u << 31)) {
+    if (nfull && aligned && bs % 64 == 0 && bs >= 256 && bs <= kRowHashMaxN) {
         ProfScope ps(prof, s, "k_sig_fast");
         hipLaunchKernelGGL(k_sig_fast, dim3(grid_for((nfull + 3) / 4 * 64, 256)), dim3(256), 0, s, d_buf, nfull,
                            (uint32_t)bs, d_weak, d_strong);
@@ -4511,12 +4511,13 @@ hipError_t launch_probe(const uint8_t* d_base, const ProbeJob* d_jobs, uint32_t 
                         uint64_t* d_pst, uint32_t* d_out, hipStream_t s, Profiler* prof, int phases) {
     if (!nprobes) return hipSuccess;
     if (fast && (n % 64 != 0 || n < 256)) return hipErrorInvalidValue;
+    const bool rows = n % 64 == 0 && n >= 256 && n <= kRowHashMaxN;  // row_hash's windows; larger: one per wave
     if (phases & 1) {
         ProfScope ps(prof, s, stride > 1 ? "k_probe_sample" : "k_probe");
-        if (fast)
+        if (fast && rows)
             hipLaunchKernelGGL(k_probe_rows<true>, dim3(grid_for((nprobes + 3) / 4 * 64, 256)), dim3(256), 0, s,
                                d_base, d_jobs, njobs, nprobes, stride, n, d_pw, d_pst);
-        else if (n % 64 == 0 && n >= 256)  // any alignment: funnel-shifted row loads
+        else if (rows)  // any alignment: funnel-shifted row loads
             hipLaunchKernelGGL(k_probe_rows<false>, dim3(grid_for((nprobes + 3) / 4 * 64, 256)), dim3(256), 0, s,
                                d_base, d_jobs, njobs, nprobes, stride, n, d_pw, d_pst);
         else
@@ -4531,16 +4532,27 @@ hipError_t launch_probe(const uint8_t* d_base, const ProbeJob* d_jobs, uint32_t 
     return hipGetLastError();
 }
 
-size_t scan_lds_bytes(uint32_t n, uint32_t* nchunks_out) {
-    const uint32_t nch = (uint32_t)((kScanTile + (uint64_t)n + 63) / 64) + 1;
-    *nchunks_out = nch;
+constexpr uint32_t scan_chunks(uint32_t n) { return (uint32_t)((kScanTile + (uint64_t)n + 63) / 64) + 1; }
+constexpr size_t scan_lds_layout(uint32_t n) {
+    const uint32_t nch = scan_chunks(n);
     const size_t pj_off = (((size_t)2 * (nch + 1) * 4) + 15) & ~(size_t)15;
     const size_t q_off = (pj_off + (size_t)(nch + 1) * 8 + 15) & ~(size_t)15;
     return q_off + (size_t)(kScanThreads / 64) * (kFQ + kWQ) * sizeof(uint2);
 }
+size_t scan_lds_bytes(uint32_t n, uint32_t* nchunks_out) {
+    *nchunks_out = scan_chunks(n);
+    return scan_lds_layout(n);
+}
 
 uint64_t scan_tile_positions() { return kTile2; }
 uint32_t scan_max_window() { return kMaxN2; }
+// k_scan keeps 16 bytes of prefix sums per 64-byte chunk of a tile plus one window in LDS
+// (scan_lds_bytes) beside 64 bytes of static LDS: the largest window whose launch fits the
+// 160 KiB of a workgroup.  Its arithmetic holds there at byte 255: the prefix of in-chunk
+// weighted sums is at most 514 080 * 7 792 chunks < 2^32, and a_ex <= 1 + 255 n.
+constexpr size_t kScanLdsMax = 160 * 1024 - 256;
+static_assert(scan_lds_layout(kScanThreadMaxN) <= kScanLdsMax && scan_lds_layout(kScanThreadMaxN + 1) > kScanLdsMax,
+              "kScanThreadMaxN is the last window whose k_scan launch fits");
 size_t scan_queue_entries() { return (size_t)kWgPerCuMax2 * 256 * (kT2 / 64) * kGFQ; }
 
 hipError_t launch_scan(const uint8_t* d_buf, const ScanSeg* d_segs, uint32_t nsegs, uint32_t ntiles, uint32_t n,
@@ -4762,7 +4774,7 @@ hipError_t launch_scan_wide(const uint8_t* d_src, uint64_t len, uint64_t pos_beg
                             uint32_t n, const DeviceIndex& ix, const uint64_t* d_strong, uint64_t* d_hit_key,
                             uint32_t* d_hit_val, uint64_t out_cap, unsigned long long* d_counters, hipStream_t s,
                             Profiler* prof) {
-    if (ix.nfiles != 1) return hipErrorInvalidValue;
+    if (ix.nfiles != 1 || n > kScanThreadMaxN) return hipErrorInvalidValue;
     ScanArgs a{};
     a.src = d_src;
     a.len = len;
