@@ -36,6 +36,7 @@
 
 #include "../../include/sydelta.h"
 #include "sydelta_host.hpp"
+#include "sydelta_stage.hpp"
 #include "sydelta_internal.hpp"
 
 using namespace sydelta;
@@ -218,6 +219,29 @@ int sydelta::host_exception() {
     }
 }
 hipStream_t sydelta::thread_stream(int device) { return thread_stream_impl(device); }
+hipStream_t sydelta::call_stream(int device, void* stream, int* dev) {
+    if (device < 0) device = 0;
+    if (dev) *dev = device;
+    return stream ? (hipStream_t)stream : thread_stream(device);
+}
+double sydelta::ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+int sydelta::batch_parts(uint64_t nops, uint64_t nfiles) {
+    return nops < kParallelOps ? 1 : (int)std::min<uint64_t>(std::max(1, walk::HostPool::get().size()), nfiles);
+}
+std::vector<std::pair<uint64_t, uint64_t>> sydelta::split_by_ops(const sydelta_delta* const* deltas, uint64_t nfiles,
+                                                                 int nparts, uint64_t nops) {
+    std::vector<std::pair<uint64_t, uint64_t>> parts(nparts);
+    uint64_t f = 0, seen = 0;
+    for (int t = 0; t < nparts; ++t) {
+        parts[t].first = f;
+        const uint64_t goal = nops / nparts * (t + 1);
+        while (f < nfiles && (t + 1 == nparts || seen < goal)) seen += deltas[f] ? deltas[f]->ops.size() : 0, ++f;
+        parts[t].second = f;
+    }
+    return parts;
+}
 uint32_t sydelta::wave_slots(int device) {
     return device >= 0 && device < kMaxPoolDevices && g_wave_slots[device] ? g_wave_slots[device] : 4096u;
 }
@@ -516,7 +540,7 @@ extern "C" int sydelta_signature_device(int device, const uint8_t* d_buf, uint64
     if (block_size == 0) return fail(SYDELTA_E_INVAL, "block_size must be > 0");
     if (len && (!d_buf || !d_weak || !d_strong)) return fail(SYDELTA_E_INVAL, "NULL device pointer");
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
+    hipStream_t s = call_stream(device, stream);
     CallProf cp;
     HIP_TRY(launch_signature(d_buf, len, block_size, d_weak, d_strong, s, cp.get()));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
@@ -575,7 +599,7 @@ extern "C" int sydelta_signature_batch_device(int device, const uint8_t* d_buf, 
     if (block_size == 0) return fail(SYDELTA_E_INVAL, "block_size must be > 0");
     if (nfiles && (!off || !len)) return fail(SYDELTA_E_INVAL, "NULL segment table");
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
+    hipStream_t s = call_stream(device, stream);
     std::vector<uint64_t> fblk(nfiles + 1, 0);
     for (uint64_t f = 0; f < nfiles; ++f) fblk[f + 1] = fblk[f] + (len[f] + block_size - 1) / block_size;
     const uint64_t total = fblk[nfiles];
@@ -1077,7 +1101,7 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
     if (nblocks >= 0xFFFFFFFFull) return fail(SYDELTA_E_INVAL, "too many blocks (%llu)", (unsigned long long)nblocks);
     SYDELTA_ENTER_DEVICE(device);
     if (device < 0) device = 0;
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device);
+    hipStream_t s = call_stream(device, stream);
     std::unique_ptr<sydelta_index, void (*)(sydelta_index*)> x(new sydelta_index(), index_release);
     x->device = device;
     x->bs = block_size;
@@ -1116,10 +1140,9 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
     ix.fwords = fw;
     ix.nslots = sl;
     const size_t nb = std::max<uint64_t>(nblocks, 1);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t sz_weak = al(4 * nb), sz_strong = al(8 * nb), sz_filt = al(4 * fw), sz_t = al(4 * sl);
-    const size_t sz_order = al(4 * nb), sz_slot = al(4 * nb), sz_files = al(sizeof(FileIx) * nfiles);
-    const size_t sz_fblk = al(8 * (nfiles + 1)), sz_cstrong = al(8 * nb);
+    const size_t sz_weak = up256(4 * nb), sz_strong = up256(8 * nb), sz_filt = up256(4 * fw), sz_t = up256(4 * sl);
+    const size_t sz_order = up256(4 * nb), sz_slot = up256(4 * nb), sz_files = up256(sizeof(FileIx) * nfiles);
+    const size_t sz_fblk = up256(8 * (nfiles + 1)), sz_cstrong = up256(8 * nb);
     // the level-1 filter of the register-fed scans (k_scan_r at bs 4096, k_scan_g at any
     // other): one file with more keys than an LDS-resident Bloom filter takes
     const bool want_narrow = nfiles == 1 && nblocks > kLdsFilterKeys;
@@ -1128,17 +1151,17 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
     const bool want_wide = nfiles == 1 && block_size > scan_max_window() && scan_wide_mode() != 0;
     const bool want_l1 = want_narrow || want_wide;
     const uint32_t l1_wshift = 1u;  // kL1WordsR words (k_scan_r / k_scan_g)
-    const size_t sz_l1 = want_l1 ? al(4 * l1_total_words(l1_wshift)) : 0;
+    const size_t sz_l1 = want_l1 ? up256(4 * l1_total_words(l1_wshift)) : 0;
     // k_scan_r's ribbon level-1 (sydelta_internal.hpp): its key lists, counts, overflow list
     // SYDELTA_L1=bloom|ribbon forces the layout (A/B measurements, parity tests at small sizes)
     const char* l1e = getenv("SYDELTA_L1");
     const bool want_rib = want_narrow && (l1e && !strcmp(l1e, "ribbon") ? true
                                           : l1e && !strcmp(l1e, "bloom") ? false
                                                                           : nblocks >= kRibMinKeys && nblocks <= kRibMaxKeys);
-    const size_t sz_rib = want_rib ? al(4ull * kL1WordsR) + al(4ull * kRibShards * kRibCap) + al(4ull * (kRibShards + 1)) +
-                                         al(4 * nb)
+    const size_t sz_rib = want_rib ? up256(4ull * kL1WordsR) + up256(4ull * kRibShards * kRibCap) + up256(4ull * (kRibShards + 1)) +
+                                         up256(4 * nb)
                                    : 0;
-    const size_t sz_fat = want_l1 ? al(16 * (size_t)sl) : 0;
+    const size_t sz_fat = want_l1 ? up256(16 * (size_t)sl) : 0;
     const size_t total = sz_weak + sz_strong + sz_filt + sz_l1 + sz_fat + 4 * sz_t + sz_order + sz_slot + sz_files +
                          sz_fblk + sz_cstrong + sz_rib;
     x->d_pool = take_kept_pool(device, total, s, &x->pool_bytes);
@@ -1156,10 +1179,10 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
         ix.l1_wshift = l1_wshift;
         if (want_rib) {  // the Bloom stays in l1; the ribbon is built on demand (scan_index)
             x->rib_mode = l1e && !strcmp(l1e, "ribbon") ? 2 : 1;
-            ix.rib_l1 = (uint32_t*)p; p += al(4ull * kL1WordsR);
-            ix.rib_keys = (uint32_t*)p; p += al(4ull * kRibShards * kRibCap);
-            ix.rib_cnt = (uint32_t*)p; p += al(4ull * (kRibShards + 1));
-            ix.rib_over = (uint32_t*)p; p += al(4 * nb);
+            ix.rib_l1 = (uint32_t*)p; p += up256(4ull * kL1WordsR);
+            ix.rib_keys = (uint32_t*)p; p += up256(4ull * kRibShards * kRibCap);
+            ix.rib_cnt = (uint32_t*)p; p += up256(4ull * (kRibShards + 1));
+            ix.rib_over = (uint32_t*)p; p += up256(4 * nb);
         }
         ix.fat = (uint4*)p; p += sz_fat;
     }
@@ -1539,17 +1562,6 @@ extern "C" void sydelta_delta_batch_free(sydelta_delta_batch* b) {
 // hit's jump, and when it does the block is scanned on demand (Classifier::walk).
 // The op list is identical whichever subset was classified first.
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
 using walk::BasisInfo;
 using walk::HitBlk;
 using walk::HitPos;
@@ -1561,7 +1573,6 @@ using walk::run_parallel;
 using walk::Src;
 using walk::walk_src;
 
-double ms_since(std::chrono::steady_clock::time_point t0);
 void finish_stats_impl(sydelta_delta* d);
 int walk_threads();
 uint64_t walk_par_min();
@@ -1740,7 +1751,7 @@ int Classifier::probe(int mode) {
         // the full pass's results stay on the device for the device walk (walk_device)
         DevBuf local;
         DevBuf& jb = stride == 1 ? probe_buf : local;
-        if (jb.p) { (void)hipFreeAsync(jb.p, s); jb.p = nullptr; }
+        jb.release();
         const size_t jbytes = (jobs.size() * sizeof(ProbeJob) + 255) & ~(size_t)255;
         const size_t obytes = (np * 4 + 255) & ~(size_t)255;
         const size_t need = jbytes + 2 * obytes + np * 8;
@@ -1754,8 +1765,7 @@ int Classifier::probe(int mode) {
             }
             jp = (uint8_t*)probe_scratch->p;
         } else {
-            HIP_TRY(dev_malloc_async(&jb.p, need, s));
-            jb.s = s;
+            HIP_TRY(jb.alloc(need, s));
             jp = (uint8_t*)jb.p;
         }
         uint32_t* d_out = (uint32_t*)(jp + jbytes);
@@ -1935,15 +1945,12 @@ int Classifier::scan(const std::vector<std::array<uint64_t, 3>>& ranges) {
     if (ntiles >= 0xFFFFFFFFull || segs.size() >= 0x7FFFFFFFull)
         return fail(SYDELTA_E_INVAL, "scan too large (%llu tiles)", (unsigned long long)ntiles);
     if (wide && ix->nfiles != 1) return fail(SYDELTA_E_INVAL, "batched match needs block_size <= %u", scan_max_window());
-    unsigned long long* d_counts = nullptr;
     DevBuf cnt_buf;
-    HIP_TRY(dev_malloc_async((void**)&d_counts, 128, s));
-    cnt_buf.p = d_counts;
-    cnt_buf.s = s;
+    HIP_TRY(cnt_buf.alloc(128, s));
+    unsigned long long* d_counts = cnt_buf.at<unsigned long long>();
     DevBuf seg_buf;
     if (!wide) {
-        HIP_TRY(dev_malloc_async(&seg_buf.p, segs.size() * sizeof(ScanSeg), s));
-        seg_buf.s = s;
+        HIP_TRY(seg_buf.alloc(segs.size() * sizeof(ScanSeg), s));
         // through the thread's pinned staging buffer: a pageable H2D of C4's 68 K segments
         // (2.7 MB) is a staged, host-blocking copy.  The previous call on this thread
         // synchronized its stream, so the buffer is free.
@@ -2125,10 +2132,6 @@ int Classifier::scan(const std::vector<std::array<uint64_t, 3>>& ranges) {
     return SYDELTA_OK;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // Scan ranges of one source, merged when closer than a scan tile (aligned-hit blocks
 // between them are scanned too: cheaper than another tile).
 void merge_ranges(std::vector<std::array<uint64_t, 3>>& r, uint64_t gap_blocks) {
@@ -2237,8 +2240,7 @@ int Classifier::phase_probe(const std::vector<std::array<uint64_t, 4>>& jobs,
     DevBuf jb;
     const size_t jbytes = (pj.size() * sizeof(ProbeJob) + 255) & ~(size_t)255;
     const size_t obytes = (np * 4 + 255) & ~(size_t)255;
-    HIP_TRY(dev_malloc_async(&jb.p, jbytes + 2 * obytes + np * 8, s));
-    jb.s = s;
+    HIP_TRY(jb.alloc(jbytes + 2 * obytes + np * 8, s));
     uint32_t* d_out = (uint32_t*)((uint8_t*)jb.p + jbytes);
     uint32_t* d_pw = (uint32_t*)((uint8_t*)jb.p + jbytes + obytes);
     uint64_t* d_pst = (uint64_t*)((uint8_t*)jb.p + jbytes + 2 * obytes);
@@ -2436,15 +2438,13 @@ int Classifier::walk_device(size_t i, uint64_t entry, const BasisInfo& bi, bool 
     const uint32_t K = chain::chain_levels(M);
     const uint64_t W = M + 2, nblk = c.probed ? c.nblk : 0;
     // one allocation: known | aflag | apfx | hpos | hblk | upos | ublk | jump | on | cnt | off | ops | res
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    const uint64_t o_known = 0, o_aflag = o_known + al(nblk), o_apfx = o_aflag + al(4 * (nblk + 1));
-    const uint64_t o_hpos = o_apfx + al(4 * (nblk + 1)), o_hblk = o_hpos + al(8 * H), o_upos = o_hblk + al(4 * H);
-    const uint64_t o_ublk = o_upos + al(8 * M), o_jump = o_ublk + al(4 * M), o_on = o_jump + al(4 * W * K);
-    const uint64_t o_cnt = o_on + al(W), o_off = o_cnt + al(4 * (M + 1)), o_ops = o_off + al(4 * (M + 1));
-    const uint64_t o_res = o_ops + al(sizeof(sydelta_op) * 2 * M), total = o_res + al(sizeof(chain::ChainResult));
+    const uint64_t o_known = 0, o_aflag = o_known + up256(nblk), o_apfx = o_aflag + up256(4 * (nblk + 1));
+    const uint64_t o_hpos = o_apfx + up256(4 * (nblk + 1)), o_hblk = o_hpos + up256(8 * H), o_upos = o_hblk + up256(4 * H);
+    const uint64_t o_ublk = o_upos + up256(8 * M), o_jump = o_ublk + up256(4 * M), o_on = o_jump + up256(4 * W * K);
+    const uint64_t o_cnt = o_on + up256(W), o_off = o_cnt + up256(4 * (M + 1)), o_ops = o_off + up256(4 * (M + 1));
+    const uint64_t o_res = o_ops + up256(sizeof(sydelta_op) * 2 * M), total = o_res + up256(sizeof(chain::ChainResult));
     DevBuf buf;
-    HIP_TRY(dev_malloc_async(&buf.p, total, s));
-    buf.s = s;
+    HIP_TRY(buf.alloc(total, s));
     uint8_t* B = (uint8_t*)buf.p;
     chain::ChainArgs a{};
     a.n = n;
@@ -2569,8 +2569,7 @@ int tail_flags(Classifier& C, const std::vector<size_t>& which, std::vector<int>
     std::vector<int> tf(tails.size(), 0);
     DevBuf tail_buf;
     const size_t bytes = (tails.size() * sizeof(TailJob) + 15) & ~(size_t)15;
-    HIP_TRY(dev_malloc_async(&tail_buf.p, bytes + tails.size() * sizeof(int), C.s));
-    tail_buf.s = C.s;
+    HIP_TRY(tail_buf.alloc(bytes + tails.size() * sizeof(int), C.s));
     int* d_flag = (int*)((uint8_t*)tail_buf.p + bytes);
     HIP_TRY(hipMemcpyAsync(tail_buf.p, tails.data(), tails.size() * sizeof(TailJob), hipMemcpyHostToDevice, C.s));
     HIP_TRY(launch_tail(C.base, (const TailJob*)tail_buf.p, (uint32_t)tails.size(), ix->d_weak, ix->d_strong, d_flag,
@@ -2653,9 +2652,8 @@ static int run_walk(sydelta_index* ix, const uint8_t* base, const std::vector<Wa
     const size_t ubytes = sizeof(WalkUnit) * nu, lbytes = 8 * nf, fout_bytes = sizeof(WalkFileOut) * nu;
     // one upload: the unit table, the last sizes and the zeroed record counter (+ the 16
     // SYDELTA_PHASE_TIMING tick counters) -- ten concurrent callers' extra copies showed
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_units = 0, o_last = ubytes, o_total = o_last + lbytes, o_fu = al(o_total + 136);
-    const size_t o_opoff = o_fu + al(4 * (nf + 1)), o_xdone = o_opoff + al(8 * (nf + 1));
+    const size_t o_units = 0, o_last = ubytes, o_total = o_last + lbytes, o_fu = up256(o_total + 136);
+    const size_t o_opoff = o_fu + up256(4 * (nf + 1)), o_xdone = o_opoff + up256(8 * (nf + 1));
     const size_t up = ex ? o_xdone + 4 * nf : o_total + 136;
     PinnedHits& ph = thread_pinned_hits();
     if (int r = pinned_at_least(ph, std::max(up, fout_bytes + 16))) return r;
@@ -2671,9 +2669,9 @@ static int run_walk(sydelta_index* ix, const uint8_t* base, const std::vector<Wa
     // expansion); host (coherent, mapped; the thread's, kept): the per-unit results and the
     // compacted records, which the kernel writes there directly -- one stream synchronisation,
     // no D2H round trips (+ the expansion's per-file results)
-    const size_t o_stage = al(up), o_fdev = o_stage + al(sizeof(WalkRec) * rec_total);
-    const size_t need = o_fdev + (ex ? al(fout_bytes) : 0);
-    const size_t m_rec = al(fout_bytes), m_res = al(m_rec + sizeof(WalkRec) * rec_total);
+    const size_t o_stage = up256(up), o_fdev = o_stage + up256(sizeof(WalkRec) * rec_total);
+    const size_t need = o_fdev + (ex ? up256(fout_bytes) : 0);
+    const size_t m_rec = up256(fout_bytes), m_res = up256(m_rec + sizeof(WalkRec) * rec_total);
     const size_t m_need = m_res + (ex ? sizeof(ExpandOut) * nf : 0);
     PinnedHits& wm = thread_walk_map();
     if (wm.bytes < m_need) {
@@ -3216,10 +3214,9 @@ int copy_heavy(sydelta_index* ix, const uint8_t* d_src, uint64_t len, hipStream_
     int cur = 0;
     HIP_TRY(hipGetDevice(&cur));
     DevScratch& sc = thread_probe_scratch(cur);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_jobs = 0, o_out1 = 256, o_pw1 = o_out1 + al(4 * np1), o_pst1 = o_pw1 + al(4 * np1);
-    const size_t o_out2 = o_pst1 + al(8 * np1), o_pw2 = o_out2 + al(4 * np2), o_pst2 = o_pw2 + al(4 * np2);
-    const size_t o_list = o_pst2 + al(8 * np2), o_cnt = o_list + al(4 * np2), need = o_cnt + 256;
+    const size_t o_jobs = 0, o_out1 = 256, o_pw1 = o_out1 + up256(4 * np1), o_pst1 = o_pw1 + up256(4 * np1);
+    const size_t o_out2 = o_pst1 + up256(8 * np1), o_pw2 = o_out2 + up256(4 * np2), o_pst2 = o_pw2 + up256(4 * np2);
+    const size_t o_list = o_pst2 + up256(8 * np2), o_cnt = o_list + up256(4 * np2), need = o_cnt + 256;
     if (sc.bytes < need) {
         if (sc.p) (void)hipFreeAsync(sc.p, s);
         sc = DevScratch();
@@ -3229,10 +3226,10 @@ int copy_heavy(sydelta_index* ix, const uint8_t* d_src, uint64_t len, hipStream_
     uint8_t* D = (uint8_t*)sc.p;
     // both samples' results come back after one synchronization: h1 | h2 | the jobs' staging
     PinnedHits& pin = thread_probe_pin();
-    if (int r = pinned_at_least(pin, al(4 * np1) + al(4 * np2) + 256)) return r;
+    if (int r = pinned_at_least(pin, up256(4 * np1) + up256(4 * np2) + 256)) return r;
     uint32_t* h1 = (uint32_t*)pin.p;
-    uint32_t* h2 = (uint32_t*)(pin.p + al(4 * np1));
-    ProbeJob* jobs = (ProbeJob*)(pin.p + al(4 * np1) + al(4 * np2));
+    uint32_t* h2 = (uint32_t*)(pin.p + up256(4 * np1));
+    ProbeJob* jobs = (ProbeJob*)(pin.p + up256(4 * np1) + up256(4 * np2));
     jobs[0] = ProbeJob{0, 0, 0, 0, 0};
     jobs[1] = ProbeJob{0, r0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(D + o_jobs, jobs, 2 * sizeof(ProbeJob), hipMemcpyHostToDevice, s));
@@ -3289,7 +3286,7 @@ extern "C" int sydelta_match_device(sydelta_index* idx, const uint8_t* d_src, ui
     if (len && !d_src) return fail(SYDELTA_E_INVAL, "NULL source");
     if (int r = check_scan_window(idx)) return r;
     SYDELTA_ENTER_DEVICE(idx->device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(idx->device);
+    hipStream_t s = call_stream(idx->device, stream);
     sydelta_delta_batch b;
     const uint64_t off = 0;
     static const bool host_timing = getenv("SYDELTA_HOST_TIMING") != nullptr;
@@ -3368,7 +3365,7 @@ extern "C" int sydelta_match_batch_device(sydelta_index* idx, const uint8_t* d_b
                                            (unsigned long long)idx->nfiles, (unsigned long long)nfiles);
     if (nfiles && (!src_off || !src_len)) return fail(SYDELTA_E_INVAL, "NULL segment table");
     SYDELTA_ENTER_DEVICE(idx->device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(idx->device);
+    hipStream_t s = call_stream(idx->device, stream);
     std::unique_ptr<sydelta_delta_batch> b(new sydelta_delta_batch());
     if (int r = match_impl(idx, d_buf, src_off, src_len, s, b.get())) return r;
     *out = b.release();
@@ -3413,7 +3410,7 @@ extern "C" int sydelta_delta_pairs_device(int device, const uint8_t* d_basis, co
     if (recs >= (1ull << 32) || fblk[nfiles] >= 0xFFFFFFFFull) return fail(SYDELTA_E_INVAL, "batch too large");
     SYDELTA_ENTER_DEVICE(device);
     if (device < 0) device = 0;
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device);
+    hipStream_t s = call_stream(device, stream);
     hipStream_t s2 = thread_aux_stream(device);
     if (!s2) return fail(SYDELTA_E_OOM, "no stream for the pairs call");
     const uint64_t nb = std::max<uint64_t>(1, fblk[nfiles]);
@@ -3427,16 +3424,11 @@ extern "C" int sydelta_delta_pairs_device(int device, const uint8_t* d_basis, co
     for (uint64_t g = 0; g < G; ++g)
         tabs.push_back(sig_batch_table(basis_off + split[g], basis_len + split[g], split[g + 1] - split[g], n,
                                        fblk[split[g]], up));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_weak = 0, o_strong = al(4 * nb), o_fblk = o_strong + al(8 * nb), need = o_fblk + 8 * up.size();
-    uint8_t* D = nullptr;
+    const size_t o_weak = 0, o_strong = up256(4 * nb), o_fblk = o_strong + up256(8 * nb), need = o_fblk + 8 * up.size();
     CallProf cp;
-    HIP_TRY(dev_malloc_async((void**)&D, need, s));
-    struct Free {  // the arrays, in s's order (the walks on s2 are joined to s before returning)
-        uint8_t* p;
-        hipStream_t s;
-        ~Free() { (void)hipFreeAsync(p, s); }
-    } free_d{D, s};
+    DevBuf free_d;  // the arrays, in s's order (the walks on s2 are joined to s before returning)
+    HIP_TRY(free_d.alloc(need, s));
+    uint8_t* D = free_d.at<uint8_t>();
     if (int r = upload_staged(D + o_fblk, up.data(), 8 * up.size(), s)) return r;
     // groups: two halves of a batch of >= 128 files (each half still fills the chip's wave
     // slots with its segments)
@@ -3508,12 +3500,11 @@ extern "C" int sydelta_compute_checksums_buf(int device, const uint8_t* buf, uin
     SYDELTA_ENTER_DEVICE(device);
     if (device < 0) device = 0;
     hipStream_t s = thread_stream(device);
-    uint8_t* d_buf = nullptr;
-    HIP_TRY(dev_malloc_async((void**)&d_buf, (len + 15) & ~15ull, s));
-    DevBuf b1; b1.p = d_buf; b1.s = s;
-    uint32_t* d_w = nullptr;
-    HIP_TRY(dev_malloc_async((void**)&d_w, nb * 12 + 16, s));
-    DevBuf b2; b2.p = d_w; b2.s = s;
+    DevBuf b1, b2;
+    HIP_TRY(b1.alloc((len + 15) & ~15ull, s));
+    HIP_TRY(b2.alloc(nb * 12 + 16, s));
+    uint8_t* d_buf = b1.at<uint8_t>();
+    uint32_t* d_w = b2.at<uint32_t>();
     uint64_t* d_st = (uint64_t*)(((uintptr_t)(d_w + nb) + 7) & ~(uintptr_t)7);
     HIP_TRY(hipMemcpyAsync(d_buf, buf, len, hipMemcpyHostToDevice, s));
     CallProf cp;
@@ -3574,8 +3565,8 @@ static int generate_from_host(int device, const uint8_t* src, uint64_t len, cons
     uint8_t* d_src = nullptr;
     DevBuf b;
     if (len) {
-        HIP_TRY(dev_malloc_async((void**)&d_src, (len + 15) & ~15ull, s));
-        b.p = d_src; b.s = s;
+        HIP_TRY(b.alloc((len + 15) & ~15ull, s));
+        d_src = b.at<uint8_t>();
         HIP_TRY(hipMemcpyAsync(d_src, src, len, hipMemcpyHostToDevice, s));
     }
     sydelta_delta_batch bt;
@@ -3775,10 +3766,8 @@ extern "C" int sydelta_compute_checksums(const char* path, uint64_t block_size, 
     PinnedPair& pin = t_stream_pinned;
     if (int r = pin.ensure(C + 16)) return r;
     DevBuf db, dw;
-    HIP_TRY(dev_malloc_async(&db.p, C + 16, s));
-    db.s = s;
-    HIP_TRY(dev_malloc_async(&dw.p, nb * 12 + 16, s));
-    dw.s = s;
+    HIP_TRY(db.alloc(C + 16, s));
+    HIP_TRY(dw.alloc(nb * 12 + 16, s));
     uint32_t* d_w = (uint32_t*)dw.p;
     uint64_t* d_st = (uint64_t*)(((uintptr_t)(d_w + nb) + 7) & ~(uintptr_t)7);
     if (int r = f.read_at(0, pin.p[0], std::min(C, L))) return r;
@@ -3880,8 +3869,7 @@ extern "C" int sydelta_generate_delta_streaming(const char* source_path, const s
     PinnedPair& pin = t_stream_pinned;
     if (int r = pin.ensure(cap + 16)) return r;
     DevBuf db;
-    HIP_TRY(dev_malloc_async(&db.p, cap + 16, s));
-    db.s = s;
+    HIP_TRY(db.alloc(cap + 16, s));
     std::unique_ptr<sydelta_delta> d(new sydelta_delta());
     d->source_size = L;
     d->block_size = n;
@@ -3960,13 +3948,10 @@ extern "C" int sydelta_apply_delta_device(int device, const uint8_t* d_basis, ui
     if (!d) return fail(SYDELTA_E_INVAL, "NULL delta");
     SYDELTA_ENTER_DEVICE(device);
     // the piece table is staged in pinned host memory (one per thread, grown on demand)
-    // so its upload runs at PCIe speed
-    struct Pinned {
-        ApplyPiece* p = nullptr;
-        size_t cap = 0;
-        ~Pinned() { if (p) (void)hipHostFree(p); }
-    };
-    static thread_local Pinned pin;
+    // so its upload runs at PCIe speed; its batches' events and the copy stream come with it
+    constexpr size_t kBatches = 8;
+    static thread_local StageRing pin(kBatches);
+    static thread_local size_t pin_cap = 0;
     static const bool host_timing = getenv("SYDELTA_HOST_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     constexpr uint64_t kSlice = 64 * 1024;
@@ -3993,47 +3978,24 @@ extern "C" int sydelta_apply_delta_device(int device, const uint8_t* d_basis, ui
         need += o.b / kSlice + (o.b % kSlice != 0);
     }
     if (pos && !d_out) return fail(SYDELTA_E_INVAL, "NULL output");
-    if (need > pin.cap) {
-        if (pin.p) { (void)hipHostFree(pin.p); pin.p = nullptr; pin.cap = 0; }
-        const size_t cap = std::max<size_t>(need, 4096) * 5 / 4;
-        HIP_TRY(hipHostMalloc((void**)&pin.p, cap * sizeof(ApplyPiece), hipHostMallocDefault));
-        pin.cap = cap;
-    }
-    ApplyPiece* pieces = pin.p;
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
+    int dev;
+    hipStream_t s = call_stream(device, stream, &dev), cstream;
     CallProf cp;
     if (need) {
+        if (need > pin_cap) pin_cap = std::max<size_t>(need, 4096) * 5 / 4;
+        HIP_TRY(pin.open(dev, pin_cap * sizeof(ApplyPiece)));
+        ApplyPiece* pieces = (ApplyPiece*)pin.base();
         // Pipelined: the host fills batch j of the piece table while batch j-1 is
-        // uploaded on a copy stream and batch j-2 is copied by k_apply on `s`.
-        constexpr size_t kBatches = 8;
-        // per thread and device, never destroyed (like thread_stream)
-        static thread_local std::map<int, std::pair<hipStream_t, std::vector<hipEvent_t>>> copy_streams;
-        auto& cs = copy_streams[device < 0 ? 0 : device];
-        if (!cs.first) HIP_TRY(hipStreamCreateWithFlags(&cs.first, hipStreamNonBlocking));
-        while (cs.second.size() < kBatches) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            cs.second.push_back(e);
-        }
-        hipStream_t cstream = cs.first;
-        const std::vector<hipEvent_t>& ev = cs.second;
+        // uploaded on a copy stream and batch j-2 is copied by k_apply on `s`.  No batch's
+        // part of the table is written twice in a call, so nothing is acquired.
         // On an error after the first upload was queued: drain both streams before the
-        // table (device) and the pinned staging (host, reused by the next call) go away
-        // (drain is declared after pb, so it runs first).
+        // table (device) and the pinned staging (host, reused by the next call) go away.
         DevBuf pb;
-        struct Drain {
-            hipStream_t a, b;
-            bool armed = false;
-            ~Drain() {
-                if (armed) { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-            }
-        } drain{cstream, s};
-        HIP_TRY(dev_malloc_async(&pb.p, need * sizeof(ApplyPiece), s));
-        pb.s = s;
-        HIP_TRY(hipEventRecord(ev[0], s));  // the table allocation is ordered before the uploads
-        HIP_TRY(hipStreamWaitEvent(cstream, ev[0], 0));
+        HIP_TRY(pb.alloc(need * sizeof(ApplyPiece), s));
+        HIP_TRY(pin.copy_stream(s, &cstream));  // the table allocation is ordered before the uploads
+        StreamDrain drain(cstream, s);
         drain.armed = true;
-        ApplyPiece* dp = (ApplyPiece*)pb.p;
+        ApplyPiece* dp = pb.at<ApplyPiece>();
         const size_t per = std::max<size_t>(1, (d->ops.size() + kBatches - 1) / kBatches);
         size_t np = 0, j = 0;
         uint64_t at = 0;
@@ -4050,8 +4012,7 @@ extern "C" int sydelta_apply_delta_device(int device, const uint8_t* d_basis, ui
             if (np == b0) continue;
             HIP_TRY(hipMemcpyAsync(dp + b0, pieces + b0, (np - b0) * sizeof(ApplyPiece), hipMemcpyHostToDevice,
                                    cstream));
-            HIP_TRY(hipEventRecord(ev[j], cstream));
-            HIP_TRY(hipStreamWaitEvent(s, ev[j], 0));
+            HIP_TRY(pin.uploaded(j, cstream, s));
             HIP_TRY(launch_apply(dp + b0, np - b0, d_basis, d_lit, d_out, s, cp.get()));
         }
         const double t_enq = ms_since(t0);
@@ -4132,7 +4093,7 @@ extern "C" int sydelta_synth_fill(uint8_t* d_buf, uint64_t len, uint64_t seed, v
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     HIP_TRY(launch_synth_fill(d_buf, len, seed, s));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SYDELTA_OK;
@@ -4146,7 +4107,7 @@ extern "C" int sydelta_synth_fill_range(uint8_t* d_buf, uint64_t first, uint64_t
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     HIP_TRY(launch_synth_fill(d_buf, len, seed, s, first));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SYDELTA_OK;
@@ -4161,7 +4122,7 @@ extern "C" int sydelta_synth_mutate_blocks(uint8_t* d_dst, const uint8_t* d_src,
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     if (len && d_dst != d_src) HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s));
     HIP_TRY(launch_synth_edit_blocks(d_dst, len, block_size, first, seed, rate_ppm, s));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
@@ -4176,7 +4137,7 @@ extern "C" int sydelta_synth_mutate(uint8_t* d_dst, const uint8_t* d_src, uint64
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     HIP_TRY(launch_synth_mutate(d_dst, d_src, len, seed, rate_ppm, s));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SYDELTA_OK;
@@ -4358,7 +4319,6 @@ int chunk_pipe_launch(sydelta_chunk* ch, uint64_t from, bool probe) {
     uint64_t rec_total = 0;
     for (const WalkUnit& u : P.units) rec_total = std::max(rec_total, u.rec_off + 2 * ((u.end - u.entry) / n) + 4);
     if (rec_total >= (1ull << 32)) return fail(SYDELTA_E_INVAL, "chunk too large for one walk");
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // device: the probe jobs, the last size and the record counter (uploaded first, for the
     // hashing), the unit table (uploaded once the first hashing is queued), the probe's
     // results, the staged records; host: the per-unit results and the compacted records
@@ -4366,15 +4326,15 @@ int chunk_pipe_launch(sydelta_chunk* ch, uint64_t from, bool probe) {
     // (the pre-roll's: per part a miss counter, zeroed with the record counter; the miss
     // list and the first hits)
     const bool preroll = probe && preroll_on() && C.ix->fblk[1] < kPreMark;
-    const size_t o_jobs = 0, o_last = al(sizeof(ProbeJob) * K), o_total = o_last + 8, o_cnt = o_total + 8;
+    const size_t o_jobs = 0, o_last = up256(sizeof(ProbeJob) * K), o_total = o_last + 8, o_cnt = o_total + 8;
     static const bool timing = getenv("SYDELTA_PHASE_TIMING") != nullptr;  // per part: 16 tick counters
     const size_t o_ticks = o_cnt + 8 * K, o_zend = o_ticks + (timing ? 128 * K : 0);
-    const size_t o_units = al(o_zend);
+    const size_t o_units = up256(o_zend);
     const size_t ubytes = sizeof(WalkUnit) * nu;
-    const size_t o_out = o_units + al(ubytes), o_pw = o_out + al(4 * np), o_pst = o_pw + al(4 * np);
-    const size_t o_list = o_pst + al(8 * np);
-    const size_t o_stage = o_list + (preroll ? al(4 * np) : 0), dneed = o_stage + al(sizeof(WalkRec) * rec_total);
-    const size_t h_rec = al(sizeof(WalkFileOut) * nu), h_end = h_rec + al(sizeof(WalkRec) * rec_total);
+    const size_t o_out = o_units + up256(ubytes), o_pw = o_out + up256(4 * np), o_pst = o_pw + up256(4 * np);
+    const size_t o_list = o_pst + up256(8 * np);
+    const size_t o_stage = o_list + (preroll ? up256(4 * np) : 0), dneed = o_stage + up256(sizeof(WalkRec) * rec_total);
+    const size_t h_rec = up256(sizeof(WalkFileOut) * nu), h_end = h_rec + up256(sizeof(WalkRec) * rec_total);
     P.on = true;  // release() undoes whatever is set below
     P.device = C.ix->device;
     P.ds = C.s;
@@ -4819,7 +4779,7 @@ extern "C" int sydelta_chunk_classify(sydelta_index* idx, const uint8_t* d_buf, 
                     (unsigned long long)(buf_pos + buf_len), (unsigned long long)need_end);
     if (buf_len && !d_buf) return fail(SYDELTA_E_INVAL, "NULL buffer");
     SYDELTA_ENTER_DEVICE(idx->device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(idx->device);
+    hipStream_t s = call_stream(idx->device, stream);
     std::unique_ptr<sydelta_chunk> ch(new sydelta_chunk());
     CallProf cp;
     Classifier& C = ch->C;
@@ -5052,8 +5012,7 @@ extern "C" int sydelta_delta_multi_device(const int* devices, int ndev, const ui
         HIP_TRY(hipSetDevice(devices[g]));
         s[g] = thread_stream(devices[g]);
         sig[g].reset(new DevBuf());
-        HIP_TRY(dev_malloc_async(&sig[g]->p, nb * 12 + 16, s[g]));
-        sig[g]->s = s[g];
+        HIP_TRY(sig[g]->alloc(nb * 12 + 16, s[g]));
         dw[g] = (uint32_t*)sig[g]->p;
         dst[g] = (uint64_t*)(((uintptr_t)(dw[g] + nb) + 7) & ~(uintptr_t)7);
         HIP_TRY(launch_signature(d_basis[g], basis_len[g], n, dw[g] + bofs[g], dst[g] + bofs[g], s[g], cp.get()));

@@ -28,14 +28,6 @@ uint64_t seg_align(uint64_t n) {
     return a;
 }
 
-struct FreeAsync {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~FreeAsync() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
 // Enqueue the hashes of files (offs, lens) of d_buf on s: d_out (device) + 32 f.  The
 // scratch is released in stream order; the caller synchronizes.
 int b3_enqueue(const uint8_t* d_buf, const uint64_t* offs, const uint64_t* lens, uint64_t nfiles, uint64_t first_chunk,
@@ -79,9 +71,8 @@ int b3_enqueue(const uint8_t* d_buf, const uint64_t* offs, const uint64_t* lens,
     const int nlevels = (int)lv_first.size() - 1;
     const uint64_t cv0 = nlevels >= 1 ? lv_total[1] : 0, cv1 = nlevels >= 2 ? lv_total[2] : 0;
     const uint64_t tab_bytes = (tab.size() * sizeof(B3Seg) + 255) / 256 * 256;
-    FreeAsync ws;
-    HIP_TRY(dev_malloc_async(&ws.p, tab_bytes + (cv0 + cv1) * 32 + 256, s));
-    ws.s = s;
+    DevBuf ws;
+    HIP_TRY(ws.alloc(tab_bytes + (cv0 + cv1) * 32 + 256, s));
     B3Seg* d_tab = (B3Seg*)ws.p;
     uint32_t* d_cv[2] = {(uint32_t*)((uint8_t*)ws.p + tab_bytes), (uint32_t*)((uint8_t*)ws.p + tab_bytes + cv0 * 32)};
     HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(B3Seg), hipMemcpyHostToDevice, s));
@@ -96,10 +87,9 @@ int b3_enqueue(const uint8_t* d_buf, const uint64_t* offs, const uint64_t* lens,
 int b3_run(int device, const uint8_t* d_buf, const uint64_t* offs, const uint64_t* lens, uint64_t nfiles,
            uint64_t first_chunk, bool root, void* stream, uint8_t* out) {
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
-    FreeAsync d_out;
-    HIP_TRY(dev_malloc_async(&d_out.p, nfiles * 32, s));
-    d_out.s = s;
+    hipStream_t s = call_stream(device, stream);
+    DevBuf d_out;
+    HIP_TRY(d_out.alloc(nfiles * 32, s));
     CallProf cp;
     if (int r = b3_enqueue(d_buf, offs, lens, nfiles, first_chunk, root, (uint8_t*)d_out.p, s, cp.get())) return r;
     HIP_TRY(hipMemcpyAsync(out, d_out.p, nfiles * 32, hipMemcpyDeviceToHost, s));
@@ -225,16 +215,14 @@ extern "C" int sydelta_blake3_file(const char* path, uint8_t out[32]) try {
     const uint64_t piece = std::min(len, kFilePiece), npieces = (len + kFilePiece - 1) / kFilePiece;
     const int nbuf = npieces > 1 ? 2 : 1;
     Pinned pin[2];
-    FreeAsync dbuf[2], d_cvs;
+    DevBuf dbuf[2], d_cvs;
     Event ev[2];
     for (int b = 0; b < nbuf; ++b) {
         HIP_TRY(hipHostMalloc((void**)&pin[b].p, piece, hipHostMallocDefault));
-        HIP_TRY(dev_malloc_async(&dbuf[b].p, piece, s));
-        dbuf[b].s = s;
+        HIP_TRY(dbuf[b].alloc(piece, s));
         HIP_TRY(hipEventCreateWithFlags(&ev[b].e, hipEventDisableTiming));
     }
-    HIP_TRY(dev_malloc_async(&d_cvs.p, npieces * 32, s));
-    d_cvs.s = s;
+    HIP_TRY(d_cvs.alloc(npieces * 32, s));
     CallProf cp;
     for (uint64_t k = 0; k < npieces; ++k) {
         const int b = (int)(k & 1);

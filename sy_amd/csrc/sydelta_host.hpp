@@ -1,9 +1,14 @@
 // sydelta_host.hpp — host-side definitions shared by the C ABI translation units
-// (sydelta_api.cpp: signature / index / match / apply; sydelta_wire.cpp: wire formats).
+// (sydelta_api.cpp: signature / index / match / apply; sydelta_wire.cpp: wire formats; the
+// batch calls sydelta_applybatch.cpp, sydelta_jsonbatch.cpp, sydelta_zstdbatch.cpp and
+// sydelta_unzstdbatch.cpp; sydelta_unzstd_api.cpp, sydelta_blake3.cpp, sydelta_integrity.cpp,
+// sydelta_local.cpp).  The pinned staging ring of the calls that upload tables is
+// sydelta_stage.hpp, which stands alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <memory>
 #include <string>
 #include <utility>
@@ -50,6 +55,58 @@ struct DeviceScope {
 int path_device(int* out);
 // The calling thread's stream for `device`.
 hipStream_t thread_stream(int device);
+// An entry point's stream: the caller's, or the calling thread's for the device (a negative
+// `device` is device 0, which *dev gets).
+hipStream_t call_stream(int device, void* stream, int* dev = nullptr);
+// One stream-ordered allocation from the library's pool (dev_malloc_async), freed on the
+// stream it was made on.
+struct DevBuf {
+    void* p = nullptr;
+    hipStream_t s = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFreeAsync(p, s);
+        p = nullptr;
+    }
+    hipError_t alloc(size_t bytes, hipStream_t stream) {
+        release();
+        const hipError_t e = dev_malloc_async(&p, bytes, stream);
+        if (e != hipSuccess) p = nullptr;
+        s = stream;
+        return e;
+    }
+    template <class T>
+    T* at(size_t off = 0) const {
+        return (T*)((uint8_t*)p + off);
+    }
+};
+// Drains its stream or streams on the way out of a call that failed after work was queued
+// (armed), before the device buffers and the pinned staging that the work reads go away.
+// Destructors run in reverse order of declaration: declare it after what it protects.
+struct StreamDrain {
+    hipStream_t a, b;
+    bool armed = false;
+    explicit StreamDrain(hipStream_t a_, hipStream_t b_ = nullptr) : a(a_), b(b_ ? b_ : a_) {}
+    StreamDrain(const StreamDrain&) = delete;
+    StreamDrain& operator=(const StreamDrain&) = delete;
+    ~StreamDrain() {
+        if (!armed) return;
+        (void)hipStreamSynchronize(a);
+        if (b != a) (void)hipStreamSynchronize(b);
+    }
+};
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+double ms_since(std::chrono::steady_clock::time_point t0);
+// A batch cut into nparts ranges [f0, f1) of files with about equal op counts (nops in all; a
+// NULL delta counts none), the last taking the rest; batch_parts: one part below
+// kParallelOps ops (the plan stays on the calling thread), else one per host pool thread.
+constexpr uint64_t kParallelOps = 1ull << 17;
+int batch_parts(uint64_t nops, uint64_t nfiles);
+std::vector<std::pair<uint64_t, uint64_t>> split_by_ops(const sydelta_delta* const* deltas, uint64_t nfiles, int nparts,
+                                                        uint64_t nops);
 // K10 wave slots of a device (CUs x 16: four waves per SIMD), from its properties at first use
 uint32_t wave_slots(int device);
 // Recount copy/data ops and literal bytes of d.

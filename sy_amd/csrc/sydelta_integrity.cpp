@@ -22,7 +22,7 @@ extern "C" int sydelta_xxh3_batch_device(int device, const uint8_t* d_buf, uint6
     }
     if (total && !d_buf) return fail(SYDELTA_E_INVAL, "NULL buffer");
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
+    hipStream_t s = call_stream(device, stream);
     // host tables: block-count prefix and the size order of the chains
     std::vector<uint64_t> pfx(nfiles + 1, 0), nb(nfiles);
     for (uint64_t f = 0; f < nfiles; ++f) {
@@ -44,21 +44,16 @@ extern "C" int sydelta_xxh3_batch_device(int device, const uint8_t* d_buf, uint6
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return nb[a] > nb[b]; });
     const uint64_t tab = nfiles * 8 * 3 + (nfiles + 1) * 8 + nact * 8 + (nact + 1) * 8 + nfiles * 4;
     const uint64_t bytes = (tab + 255) / 256 * 256 + xxh_chain_records(npieces) * 64;
-    void* ws = nullptr;
-    HIP_TRY(dev_malloc_async(&ws, bytes, s));
-    struct Free {
-        void* p;
-        hipStream_t s;
-        ~Free() { (void)hipFreeAsync(p, s); }
-    } fr{ws, s};
-    uint64_t* d_off = (uint64_t*)ws;
+    DevBuf ws;
+    HIP_TRY(ws.alloc(bytes, s));
+    uint64_t* d_off = ws.at<uint64_t>();
     uint64_t* d_len = d_off + nfiles;
     uint64_t* d_out = d_len + nfiles;
     uint64_t* d_pfx = d_out + nfiles;
     uint64_t* d_aoff = d_pfx + nfiles + 1;
     uint64_t* d_apfx = d_aoff + nact;
     uint32_t* d_order = (uint32_t*)(d_apfx + nact + 1);
-    uint64_t* d_C = (uint64_t*)((uint8_t*)ws + (tab + 255) / 256 * 256);
+    uint64_t* d_C = ws.at<uint64_t>((tab + 255) / 256 * 256);
     HIP_TRY(hipMemcpyAsync(d_off, offs, nfiles * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_len, lens, nfiles * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_pfx, pfx.data(), (nfiles + 1) * 8, hipMemcpyHostToDevice, s));

@@ -1,56 +1,28 @@
 // sydelta_jsonbatch.cpp — sydelta_delta_batch_to_json_device: serde_json::to_string(&Delta)
 // (ssh.rs:1003) for a batch of deltas.  The host validates every file and cuts its ops into
 // tiles (sydelta_jsonbatch.hpp; on the shared host pool when the batch is large), then feeds
-// the tile and pair tables to the device in slices through a ring of pinned buffers: half a
-// ring of slices is filled while the half before it is uploaded and sized.
+// the tile and pair tables to the device in slices through the calling thread's pinned ring
+// (sydelta_stage.hpp; kRing slices of kSliceBytes, whatever the batch): half a ring of slices
+// is filled while the half before it is uploaded and sized.
 // Placing the texts, the decision whether the arena holds them, and the writing are queued
 // behind the last slice without a wait; the call waits for the stream once, at the end.
 #include <limits.h>
 
 #include <algorithm>
-#include <chrono>
-#include <map>
 
 #include "sydelta_host.hpp"
+#include "sydelta_stage.hpp"
 #include "sydelta_jsonbatch.hpp"
 
 using namespace sydelta;
 
 namespace {
 
-struct FreeAsync {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~FreeAsync() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
-// The calling thread's pinned ring (kRing slices of kSliceBytes, whatever the batch), and per
-// device the events of the slices' uploads (never destroyed, like thread_stream).
-struct Ring {
-    uint8_t* p = nullptr;
-    ~Ring() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-struct Uploads {
-    hipEvent_t up[jsonb::kRing] = {};
-};
-thread_local Ring t_ring;
-thread_local std::map<int, Uploads> t_up;
+thread_local StageRing t_ring(jsonb::kRing);
 
 jsonb::FileIn file_in(const sydelta_delta* d, uint64_t lit_off, uint64_t lit_len) {
     return jsonb::FileIn{d && !d->ops.empty() ? d->ops.data() : nullptr, d ? d->ops.size() : 0, d != nullptr,
                          d ? d->source_size : 0, d ? d->block_size : 0, lit_off, lit_len};
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-constexpr uint64_t kParallelOps = 1ull << 17;  // below: the plan stays on the calling thread
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace
@@ -88,21 +60,14 @@ extern "C" int sydelta_delta_batch_to_json_device(int device, const sydelta_delt
     // 1. validate every file and count its tiles and pairs: parts of about equal op counts
     uint64_t nops = 0;
     for (uint64_t f = 0; f < nfiles; ++f) nops += deltas[f] ? deltas[f]->ops.size() : 0;
-    const int nparts = nops < kParallelOps ? 1 : (int)std::min<uint64_t>(std::max(1, walk::HostPool::get().size()), nfiles);
+    const int nparts = batch_parts(nops, nfiles);
     struct Part {
         uint64_t f0 = 0, f1 = 0, literal = 0;
         jsonb::Err err;
     };
     std::vector<Part> parts(nparts);
-    {
-        uint64_t f = 0, seen = 0;
-        for (int t = 0; t < nparts; ++t) {
-            parts[t].f0 = f;
-            const uint64_t goal = nops / nparts * (t + 1);
-            while (f < nfiles && (t + 1 == nparts || seen < goal)) seen += deltas[f] ? deltas[f]->ops.size() : 0, ++f;
-            parts[t].f1 = f;
-        }
-    }
+    const auto ranges = split_by_ops(deltas, nfiles, nparts, nops);
+    for (int t = 0; t < nparts; ++t) parts[t].f0 = ranges[t].first, parts[t].f1 = ranges[t].second;
     std::vector<jsonb::FileIn> files(nfiles);
     std::vector<jsonb::Count> fc(nfiles);
     if (!walk::run_parallel(nparts, [&](int t) {
@@ -145,29 +110,18 @@ extern "C" int sydelta_delta_batch_to_json_device(int device, const sydelta_delt
     const double t_plan = ms_since(t_start);
 
     // 2. the device tables
-    const int dev = device < 0 ? 0 : device;
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    int dev;
+    hipStream_t s = call_stream(device, stream, &dev);
     CallProf cp;
-    if (!t_ring.p) HIP_TRY(hipHostMalloc((void**)&t_ring.p, jsonb::kRing * jsonb::kSliceBytes, hipHostMallocDefault));
-    Uploads& ups = t_up[dev];
-    for (hipEvent_t& e : ups.up)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(t_ring.open(dev, jsonb::kRing * jsonb::kSliceBytes));
     const size_t b_tiles = up256(cnt.tiles * sizeof(jsonb::Tile)), b_pairs = up256(cnt.pairs * sizeof(jsonb::Pair)),
                  b_t8 = up256(cnt.tiles * 8), b_f8 = up256((nfiles + 1) * 8);
     // On an error after the first upload was queued: the stream is drained before the tables
-    // (device) and the ring (host, reused by the next call) go away (drain is declared after
-    // tab, so it runs first).
-    FreeAsync tab;
-    struct Drain {
-        hipStream_t s;
-        bool armed = false;
-        ~Drain() {
-            if (armed) (void)hipStreamSynchronize(s);
-        }
-    } drain{s};
-    HIP_TRY(dev_malloc_async(&tab.p, b_tiles + b_pairs + 2 * b_t8 + 2 * b_f8 + up256(2 * nfiles * 8), s));
-    tab.s = s;
-    uint8_t* at = (uint8_t*)tab.p;
+    // (device) and the ring (host, reused by the next call) go away.
+    DevBuf tab;
+    StreamDrain drain(s);
+    HIP_TRY(tab.alloc(b_tiles + b_pairs + 2 * b_t8 + 2 * b_f8 + up256(2 * nfiles * 8), s));
+    uint8_t* at = tab.at<uint8_t>();
     jsonb::Tile* d_tiles = (jsonb::Tile*)at;
     jsonb::Pair* d_pairs = (jsonb::Pair*)(at += b_tiles);
     uint64_t* d_len = (uint64_t*)(at += b_pairs);
@@ -181,18 +135,16 @@ extern "C" int sydelta_delta_batch_to_json_device(int device, const sydelta_delt
     // large) while the other half uploads, then uploaded and sized in order
     constexpr uint32_t kGroup = jsonb::kRing / 2;
     const uint64_t nslices = slices.size();
-    uint8_t* const ring = t_ring.p;  // the calling thread's: the pool's threads have their own t_ring
-    for (uint64_t j0 = 0, g = 0; j0 < nslices; j0 += kGroup, ++g) {
+    for (uint64_t j0 = 0; j0 < nslices; j0 += kGroup) {
         const int n = (int)std::min<uint64_t>(kGroup, nslices - j0);
-        const uint32_t slot0 = (uint32_t)(g % 2) * kGroup;
-        if (g >= 2)
-            for (int k = 0; k < n; ++k) HIP_TRY(hipEventSynchronize(ups.up[slot0 + k]));  // the slots' previous uploads
+        void* slot[kGroup];  // of the calling thread's ring: the pool's threads have their own t_ring
+        for (int k = 0; k < n; ++k) HIP_TRY(t_ring.acquire(j0 + k, &slot[k]));
         int bad[kGroup] = {};
         const int par = nparts > 1 ? n : 1;
         if (!walk::run_parallel(par, [&](int k) {
                 for (int i = k; i < n; i += par) {
                     const SliceAt& a = slices[j0 + i];
-                    jsonb::Tile* ht = (jsonb::Tile*)(ring + (slot0 + i) * jsonb::kSliceBytes);
+                    jsonb::Tile* ht = (jsonb::Tile*)slot[i];
                     jsonb::Cursor c = a.c;
                     jsonb::Slice sl;
                     jsonb::next_slice(files.data(), fc.data(), nfiles, c, a.p0, ht, (jsonb::Pair*)(ht + jsonb::kSliceTiles), &sl);
@@ -203,12 +155,12 @@ extern "C" int sydelta_delta_batch_to_json_device(int device, const sydelta_delt
         for (int k = 0; k < n; ++k) {
             const SliceAt& a = slices[j0 + k];
             if (bad[k]) return fail(SYDELTA_E_INVAL, "internal: slice count");
-            jsonb::Tile* ht = (jsonb::Tile*)(ring + (slot0 + k) * jsonb::kSliceBytes);
+            jsonb::Tile* ht = (jsonb::Tile*)slot[k];
             jsonb::Pair* hp = (jsonb::Pair*)(ht + jsonb::kSliceTiles);
             drain.armed = true;
             HIP_TRY(hipMemcpyAsync(d_tiles + a.t0, ht, a.sl.ntiles * sizeof(jsonb::Tile), hipMemcpyHostToDevice, s));
             HIP_TRY(hipMemcpyAsync(d_pairs + a.p0, hp, a.sl.npairs * sizeof(jsonb::Pair), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipEventRecord(ups.up[slot0 + k], s));
+            HIP_TRY(t_ring.uploaded(j0 + k, s));
             HIP_TRY(launch_jsonb_len(d_tiles, d_pairs, a.t0, a.sl.ntiles, d_lit, d_len, s, cp.get()));
         }
     }

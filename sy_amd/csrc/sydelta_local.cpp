@@ -16,16 +16,6 @@
 
 using namespace sydelta;
 
-namespace {
-struct DevMem {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~DevMem() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-}  // namespace
-
 // local.rs:549-619: for every block of the source, whether it differs from the same
 // block of the destination; stats as the loop counts them (changed_blocks,
 // literal_bytes = bytes of changed blocks, bytes_written = source size).
@@ -36,7 +26,7 @@ extern "C" int sydelta_block_compare_device(int device, const uint8_t* d_src, ui
     if (src_len && (!d_src || !d_changed)) return fail(SYDELTA_E_INVAL, "NULL buffer");
     if (dst_len && !d_dst) return fail(SYDELTA_E_INVAL, "NULL destination");
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
+    hipStream_t s = call_stream(device, stream);
     const uint64_t nb = (src_len + block_size - 1) / block_size;
     CallProf cp;
     HIP_TRY(launch_block_cmp(d_src, src_len, d_dst, dst_len, block_size, d_changed, s, cp.get()));
@@ -96,10 +86,9 @@ extern "C" int sydelta_estimate_change_ratio_device(int device, const uint8_t* d
     const std::vector<uint64_t> pos = sample_blocks(want, total_blocks);
     if (!want) return finish(0.0, 0, 0);
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
-    DevMem m;
-    HIP_TRY(dev_malloc_async(&m.p, want * 8 * 3, s));
-    m.s = s;
+    hipStream_t s = call_stream(device, stream);
+    DevBuf m;
+    HIP_TRY(m.alloc(want * 8 * 3, s));
     uint64_t* d_pos = (uint64_t*)m.p;
     uint64_t* d_hs = d_pos + want;
     uint64_t* d_hd = d_hs + want;
@@ -184,9 +173,8 @@ extern "C" int sydelta_estimate_change_ratio(const char* source_path, const char
     hipStream_t s = thread_stream(dev);
     const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(want, (64ull << 20) / block_size));
     std::vector<uint8_t> host(2 * per * block_size);
-    DevMem m;
-    HIP_TRY(dev_malloc_async(&m.p, host.size(), s));
-    m.s = s;
+    DevBuf m;
+    HIP_TRY(m.alloc(host.size(), s));
     uint64_t changed = 0;
     std::vector<uint64_t> offs, lens, hash;
     std::vector<uint64_t> rs(per), rd(per);

@@ -726,6 +726,33 @@ struct UnzArgs {
     unz::Totals* tot;
     unsigned long long* status;
 };
+// The decode scratch behind UnzArgs / UnzbArgs for these counts, every region on a 256-byte
+// boundary; bpos holds nb + bpos_extra words (1 for a frame, nfiles for a batch).
+struct UnzScratch {
+    uint64_t blocks, huf, fse, lits, seqs, exit, entry, bpos, changed, total;
+    UnzScratch(uint64_t nb, uint64_t nhuf, uint64_t nfse, uint64_t nlit, uint64_t nseq, uint64_t bpos_extra) {
+        uint64_t at = 0;
+        auto take = [&at](uint64_t bytes) {
+            const uint64_t o = at;
+            at += (bytes + 255) & ~(uint64_t)255;
+            return o;
+        };
+        blocks = take(nb * sizeof(unz::Block)), huf = take(nhuf * sizeof(unz::HufTab)), fse = take(nfse * sizeof(unz::FseTab));
+        lits = take(nlit), seqs = take(nseq * sizeof(unz::Seq)), exit = take(nb * sizeof(unz::Hist)), entry = take(nb * 12);
+        bpos = take((nb + bpos_extra) * 8), changed = take(4 * kUnzRounds), total = at;
+    }
+    template <class Args>
+    void point(Args& a, uint8_t* W) const {
+        a.blocks = (unz::Block*)(W + blocks);
+        a.huf = (unz::HufTab*)(W + huf);
+        a.fse = (unz::FseTab*)(W + fse);
+        a.lits = W + lits;
+        a.seqs = (unz::Seq*)(W + seqs);
+        a.exit = (unz::Hist*)(W + exit);
+        a.entry = (uint32_t*)(W + entry);
+        a.bpos = (uint64_t*)(W + bpos);
+    }
+};
 // Stage 1 (d_blocks NULL: the counts alone).
 hipError_t launch_unz_scan(const uint8_t* d_in, uint64_t len, unz::Block* d_blocks, uint64_t cap, unz::Totals* d_tot,
                            unsigned long long* d_status, hipStream_t s, Profiler* prof);

@@ -11,14 +11,6 @@ using namespace sydelta;
 
 namespace {
 
-struct FreeAsync {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~FreeAsync() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
 int frame_error(uint64_t status) {
     return fail(SYDELTA_E_INVAL, "zstd frame: block %llu: %s", (unsigned long long)(status >> 32),
                 unz::err_text((uint32_t)status));
@@ -33,16 +25,14 @@ extern "C" int sydelta_zstd_decompress_device(int device, const uint8_t* d_in, u
     if (len < 4) return frame_error(unz::ekey(0, unz::kTrunc));
     if (!d_in) return fail(SYDELTA_E_INVAL, "NULL input");
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
+    hipStream_t s = call_stream(device, stream);
     CallProf cp;
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
 
     // the counts
-    FreeAsync head;
-    HIP_TRY(dev_malloc_async(&head.p, 512, s));
-    head.s = s;
-    unz::Totals* d_tot = (unz::Totals*)head.p;
-    unsigned long long* d_status = (unsigned long long*)((uint8_t*)head.p + 256);
+    DevBuf head;
+    HIP_TRY(head.alloc(512, s));
+    unz::Totals* d_tot = head.at<unz::Totals>();
+    unsigned long long* d_status = head.at<unsigned long long>(256);
     struct {
         unz::Totals t;
         unsigned long long status;
@@ -57,26 +47,13 @@ extern "C" int sydelta_zstd_decompress_device(int device, const uint8_t* d_in, u
     if (c.nb > 0x7FFFFFFFull) return fail(SYDELTA_E_INVAL, "zstd frame: too many blocks");
 
     // tables, entropy decode, stitch, offsets
-    const uint64_t o_blocks = 0, o_huf = o_blocks + al(c.nb * sizeof(unz::Block)),
-                   o_fse = o_huf + al(c.nhuf * sizeof(unz::HufTab)), o_lits = o_fse + al(c.nfse * sizeof(unz::FseTab)),
-                   o_seqs = o_lits + al(c.nlit), o_exit = o_seqs + al(c.nseq * sizeof(unz::Seq)),
-                   o_entry = o_exit + al(c.nb * sizeof(unz::Hist)), o_bpos = o_entry + al(c.nb * 12),
-                   o_changed = o_bpos + al((c.nb + 1) * 8), total = o_changed + al(4 * kUnzRounds);
-    FreeAsync ws;
-    HIP_TRY(dev_malloc_async(&ws.p, total, s));
-    ws.s = s;
-    uint8_t* W = (uint8_t*)ws.p;
+    const UnzScratch L(c.nb, c.nhuf, c.nfse, c.nlit, c.nseq, 1);
+    DevBuf ws;
+    HIP_TRY(ws.alloc(L.total, s));
     UnzArgs a{};
     a.in = d_in;
-    a.blocks = (unz::Block*)(W + o_blocks);
+    L.point(a, ws.at<uint8_t>());
     a.nb = c.nb;
-    a.huf = (unz::HufTab*)(W + o_huf);
-    a.fse = (unz::FseTab*)(W + o_fse);
-    a.lits = W + o_lits;
-    a.seqs = (unz::Seq*)(W + o_seqs);
-    a.exit = (unz::Hist*)(W + o_exit);
-    a.entry = (uint32_t*)(W + o_entry);
-    a.bpos = (uint64_t*)(W + o_bpos);
     a.tot = d_tot;
     a.status = d_status;
     HIP_TRY(launch_unz_scan(d_in, len, a.blocks, c.nb, d_tot, d_status, s, cp.get()));
@@ -90,10 +67,9 @@ extern "C" int sydelta_zstd_decompress_device(int device, const uint8_t* d_in, u
     if (!d_out || out_cap < n || !n) return SYDELTA_OK;
 
     // place, pointer doubling, gather
-    FreeAsync par;
-    HIP_TRY(dev_malloc_async(&par.p, n * 4, s));
-    par.s = s;
-    HIP_TRY(launch_unz_place(a, n, d_out, (uint32_t*)par.p, (uint32_t*)(W + o_changed), s, cp.get()));
+    DevBuf par;
+    HIP_TRY(par.alloc(n * 4, s));
+    HIP_TRY(launch_unz_place(a, n, d_out, par.at<uint32_t>(), ws.at<uint32_t>(L.changed), s, cp.get()));
     HIP_TRY(hipStreamSynchronize(s));
     return SYDELTA_OK;
 } catch (...) {

@@ -177,13 +177,6 @@ struct Reader {
         return true;
     }
 };
-struct DevBuf_wire {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~DevBuf_wire() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
 }  // namespace
 
 // serde_json::to_string(&Vec<BlockChecksum>)  (sy-remote.rs:147, without println's '\n')
@@ -439,7 +432,7 @@ extern "C" int sydelta_delta_to_json_device(const sydelta_delta* d, const uint8_
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     struct Pinned {
         JsonPiece* p = nullptr;
         size_t cap = 0;
@@ -482,12 +475,11 @@ extern "C" int sydelta_delta_to_json_device(const sydelta_delta* d, const uint8_
     static const char kHead[] = "{\"ops\":[";
     uint64_t body = 0;
     CallProf cp;
-    DevBuf_wire buf;
+    DevBuf buf;
     if (np) {
         const size_t pb = (np * sizeof(JsonPiece) + 255) & ~(size_t)255;
         const size_t lb = (np * 8 + 255) & ~(size_t)255;
-        HIP_TRY(dev_malloc_async(&buf.p, pb + lb + np * 8, s));
-        buf.s = s;
+        HIP_TRY(buf.alloc(pb + lb + np * 8, s));
         JsonPiece* d_pieces = (JsonPiece*)buf.p;
         uint64_t* d_len = (uint64_t*)((uint8_t*)buf.p + pb);
         uint64_t* d_off = (uint64_t*)((uint8_t*)buf.p + pb + lb);
@@ -544,7 +536,7 @@ extern "C" int sydelta_checksums_to_json_device(const uint32_t* d_weak, const ui
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     uint64_t lo = 0, hi = 0;
     sigjson::text_bounds(n, block_size, last_size, lo, hi);
     if (n == 0) {
@@ -558,9 +550,8 @@ extern "C" int sydelta_checksums_to_json_device(const uint32_t* d_weak, const ui
     const sigjson::SigArgs a{d_weak, d_strong, n, block_size, last_size};
     const uint64_t nt = (n + sigjson::kTile - 1) / sigjson::kTile;
     CallProf cp;
-    DevBuf_wire buf;
-    HIP_TRY(dev_malloc_async(&buf.p, 2 * nt * 8, s));
-    buf.s = s;
+    DevBuf buf;
+    HIP_TRY(buf.alloc(2 * nt * 8, s));
     uint64_t* d_tlen = (uint64_t*)buf.p;
     uint64_t* d_toff = d_tlen + nt;
     HIP_TRY(launch_sigjson_len(a, d_tlen, s, cp.get()));
@@ -597,12 +588,11 @@ extern "C" int sydelta_checksums_from_json_device(const uint8_t* d_text, uint64_
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     const uint64_t nc = (len + sigjson::kParseChunk - 1) / sigjson::kParseChunk;
     CallProf cp;
-    DevBuf_wire buf;
-    HIP_TRY(dev_malloc_async(&buf.p, 2 * nc * 8 + 8, s));
-    buf.s = s;
+    DevBuf buf;
+    HIP_TRY(buf.alloc(2 * nc * 8 + 8, s));
     uint64_t* d_cnt = (uint64_t*)buf.p;
     uint64_t* d_rank = d_cnt + nc;
     unsigned long long* d_bad = (unsigned long long*)(d_rank + nc);
@@ -661,7 +651,7 @@ extern "C" int sydelta_delta_from_json_device(const uint8_t* d_text, uint64_t le
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    hipStream_t s = call_stream(dev, stream);
     // head and tail (the tail is < 80 bytes: two u64 and the keys)
     char head[dparse::kHead], tail[96];
     const uint64_t tl = std::min<uint64_t>(len - dparse::kHead, sizeof tail);
@@ -688,10 +678,9 @@ extern "C" int sydelta_delta_from_json_device(const uint8_t* d_text, uint64_t le
     dparse::DArgs a{d_text, E, (E - dparse::kHead + dparse::kChunk - 1) / dparse::kChunk};
     uint64_t nops = 0, nlit = 0;
     CallProf cp;
-    DevBuf_wire buf;
+    DevBuf buf;
     const uint64_t nc = a.nc;
-    HIP_TRY(dev_malloc_async(&buf.p, (4 * (nc + 1) + 1) * 8, s));
-    buf.s = s;
+    HIP_TRY(buf.alloc((4 * (nc + 1) + 1) * 8, s));
     uint64_t* d_ocnt = (uint64_t*)buf.p;
     uint64_t* d_lcnt = d_ocnt + nc + 1;
     uint64_t* d_orank = d_lcnt + nc + 1;
@@ -716,9 +705,8 @@ extern "C" int sydelta_delta_from_json_device(const uint8_t* d_text, uint64_t le
     d->source_size = src_size;
     d->block_size = blk;
     if (nops) {
-        DevBuf_wire ob;
-        HIP_TRY(dev_malloc_async(&ob.p, nops * (8 + sizeof(sydelta_op)), s));
-        ob.s = s;
+        DevBuf ob;
+        HIP_TRY(ob.alloc(nops * (8 + sizeof(sydelta_op)), s));
         uint64_t* d_pos = (uint64_t*)ob.p;
         sydelta_op* d_ops = (sydelta_op*)(d_pos + nops);
         HIP_TRY(launch_dparse_place(a, d_orank, d_pos, s, cp.get()));
@@ -760,7 +748,7 @@ extern "C" int sydelta_zstd_compress_device(int device, const uint8_t* d_in, uin
                     (unsigned long long)out_cap, (unsigned long long)len,
                     (unsigned long long)zstd::frame_bound(len));
     SYDELTA_ENTER_DEVICE(device);
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(device < 0 ? 0 : device);
+    hipStream_t s = call_stream(device, stream);
     if (len == 0) {  // one empty Raw block, the last
         uint8_t f[zstd::kFrameHeader + 3];
         zstd::frame_header(f, 0);
@@ -776,24 +764,22 @@ extern "C" int sydelta_zstd_compress_device(int device, const uint8_t* d_in, uin
     uint64_t kBatch = 4096;
     if (const char* e = getenv("SYDELTA_ZSTD_BATCH"))
         if (const uint64_t v = strtoull(e, nullptr, 10)) kBatch = std::min<uint64_t>(v, 1 << 20);
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
     uint64_t nb_max, o_lz, o_size, o_type, o_len, o_off, total;
-    DevBuf_wire buf;
+    DevBuf buf;
     for (;;) {  // a device short of memory gets smaller batches (down to 64 blocks)
         nb_max = std::min<uint64_t>(nblocks, kBatch);
-        o_lz = al(nb_max * zstd::kBlockMax);
-        o_size = o_lz + al(nb_max * zstd::kSeqScratchBytes);
-        o_type = o_size + al(4 * nb_max);
-        o_len = o_type + al(4 * nb_max);
-        o_off = o_len + al(8 * nb_max);
-        total = o_off + al(8 * nb_max);
-        const hipError_t e = dev_malloc_async(&buf.p, total, s);
+        o_lz = up256(nb_max * zstd::kBlockMax);
+        o_size = o_lz + up256(nb_max * zstd::kSeqScratchBytes);
+        o_type = o_size + up256(4 * nb_max);
+        o_len = o_type + up256(4 * nb_max);
+        o_off = o_len + up256(8 * nb_max);
+        total = o_off + up256(8 * nb_max);
+        const hipError_t e = buf.alloc(total, s);
         if (e == hipSuccess) break;
         if (e != hipErrorOutOfMemory || kBatch <= 64) HIP_TRY(e);
         (void)hipGetLastError();
         kBatch /= 2;
     }
-    buf.s = s;
     uint8_t* B = (uint8_t*)buf.p;
     uint8_t* d_lz = B + o_lz;
     uint32_t* d_size = (uint32_t*)(B + o_size);

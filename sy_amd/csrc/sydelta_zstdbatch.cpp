@@ -5,45 +5,18 @@
 // written.  Nothing is read back between rounds; the call waits for the stream once, at its
 // end, for the frames' offsets and the total.
 #include <algorithm>
-#include <chrono>
-#include <map>
 
 #include "sydelta_host.hpp"
+#include "sydelta_stage.hpp"
 #include "sydelta_zstdbatch.hpp"
 
 using namespace sydelta;
 
 namespace {
 
-struct FreeAsync {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~FreeAsync() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
-// The calling thread's pinned staging (kStageSlots slots of kStageFiles table entries, whatever
-// the batch), and per device the events of the slots' uploads (never destroyed, like
-// thread_stream).
-struct Stage {
-    zstdb::File* p = nullptr;
-    ~Stage() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-struct Uploads {
-    hipEvent_t up[zstdb::kStageSlots] = {};
-};
-thread_local Stage t_stage;
-thread_local std::map<int, Uploads> t_up;
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
+// The calling thread's pinned staging (sydelta_stage.hpp): kStageSlots slots of kStageFiles
+// table entries, whatever the batch.
+thread_local StageRing t_stage(zstdb::kStageSlots);
 }  // namespace
 
 extern "C" uint64_t sydelta_zstd_batch_bound(const uint64_t* text_len, uint64_t nfiles) {
@@ -71,8 +44,8 @@ extern "C" int sydelta_zstd_compress_batch_device(int device, const uint8_t* d_i
     if (zstdb::plan((uintptr_t)d_in, in_buf_len, text_off, text_len, nfiles, &files, &nblocks, &err))
         return fail(err.code, "%s", err.msg.c_str());
     SYDELTA_ENTER_DEVICE(device);
-    const int dev = device < 0 ? 0 : device;
-    hipStream_t s = stream ? (hipStream_t)stream : thread_stream(dev);
+    int dev;
+    hipStream_t s = call_stream(device, stream, &dev);
     const double t_plan = ms_since(t_start);
 
     // 2. one allocation: a round's slots and scratch, its tables, the file table, the frames'
@@ -81,7 +54,7 @@ extern "C" int sydelta_zstd_compress_batch_device(int device, const uint8_t* d_i
     const size_t b_files = up256(nfiles * sizeof(zstdb::File)), b_foff = up256((nfiles + 3) * 8);
     uint64_t nb_max;
     size_t o_lz, o_size, o_type, o_len, o_off, o_files, o_foff;
-    FreeAsync buf;
+    DevBuf buf;
     for (;;) {  // a device short of memory gets smaller rounds
         nb_max = std::min<uint64_t>(nblocks, round);
         o_lz = up256(nb_max * zstd::kBlockMax);
@@ -91,14 +64,13 @@ extern "C" int sydelta_zstd_compress_batch_device(int device, const uint8_t* d_i
         o_off = o_len + up256(8 * nb_max);
         o_files = o_off + up256(8 * nb_max);
         o_foff = o_files + b_files;
-        const hipError_t e = dev_malloc_async(&buf.p, o_foff + b_foff, s);
+        const hipError_t e = buf.alloc(o_foff + b_foff, s);
         if (e == hipSuccess) break;
         if (e != hipErrorOutOfMemory || round <= zstdb::kRoundMin) HIP_TRY(e);
         (void)hipGetLastError();
         round /= 2;
     }
-    buf.s = s;
-    uint8_t* const B = (uint8_t*)buf.p;
+    uint8_t* const B = buf.at<uint8_t>();
     uint8_t* const d_lz = B + o_lz;
     uint32_t* const d_size = (uint32_t*)(B + o_size);
     uint32_t* const d_type = (uint32_t*)(B + o_type);
@@ -111,31 +83,13 @@ extern "C" int sydelta_zstd_compress_batch_device(int device, const uint8_t* d_i
 
     // On an error after the first upload was queued the stream is drained before the scratch
     // (device) and the staging (host, reused by the next call) go away.
-    struct Drain {
-        hipStream_t s;
-        bool armed = false;
-        ~Drain() {
-            if (armed) (void)hipStreamSynchronize(s);
-        }
-    } drain{s};
+    StreamDrain drain(s);
 
     // 3. the file table, a staging slot at a time
-    if (!t_stage.p)
-        HIP_TRY(hipHostMalloc((void**)&t_stage.p, (size_t)zstdb::kStageSlots * zstdb::kStageFiles * sizeof(zstdb::File),
-                              hipHostMallocDefault));
-    Uploads& ups = t_up[dev];
-    for (hipEvent_t& e : ups.up)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (uint64_t f0 = 0, k = 0; f0 < nfiles; f0 += zstdb::kStageFiles, ++k) {
-        const uint64_t n = std::min<uint64_t>(zstdb::kStageFiles, nfiles - f0);
-        const uint32_t slot = (uint32_t)(k % zstdb::kStageSlots);
-        if (k >= zstdb::kStageSlots) HIP_TRY(hipEventSynchronize(ups.up[slot]));  // the slot's previous upload
-        zstdb::File* h = t_stage.p + (size_t)slot * zstdb::kStageFiles;
-        std::copy(files.begin() + f0, files.begin() + f0 + n, h);
-        drain.armed = true;
-        HIP_TRY(hipMemcpyAsync(d_files + f0, h, n * sizeof(zstdb::File), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ups.up[slot], s));
-    }
+    HIP_TRY(t_stage.open(dev, (size_t)zstdb::kStageSlots * zstdb::kStageFiles * sizeof(zstdb::File)));
+    uint64_t slot_uses = 0;
+    drain.armed = true;
+    HIP_TRY(t_stage.upload(files.data(), files.size(), d_files, &slot_uses, s));
     HIP_TRY(hipMemsetAsync(d_base, 0, 16, s));
 
     // 4. the rounds: round r reads its base from word r % 2 and leaves the next one's in the
