@@ -497,6 +497,65 @@ int sydelta_checksums_from_json_device(const uint8_t *d_text, uint64_t len, syde
  * those with sydelta_delta_from_json. */
 int sydelta_delta_from_json_device(const uint8_t *d_text, uint64_t len, uint8_t *d_lit, uint64_t lit_cap,
                                    uint64_t *lit_len, sydelta_delta **out, void *stream);
+/* serde_json::from_str::<Delta> (sy-remote.rs:175) for nfiles texts in one call: the receiver's
+ * step between sydelta_zstd_decompress_batch_device's text arena and
+ * sydelta_apply_delta_batch_device.
+ * File f: its result is exactly what sydelta_delta_from_json_device gives for the text
+ *         d_text[text_off[f], +text_len[f]) alone: the same ops, source_size, block_size and
+ *         stats, and the same literal bytes in op order, at d_lit[lit_off[f], +lit_len[f]).
+ *         Its Data ops index that range (op.a = the offset of the op's first byte inside it),
+ *         as sydelta_apply_delta_batch_device reads them with lit_off and lit_len passed on
+ *         unchanged.
+ *  - Inputs: text_off, text_len, lit_off, lit_len and file_status are host arrays of nfiles
+ *    entries.  d_text, d_lit and every text_off[f] may have any alignment.  Texts may overlap,
+ *    repeat or come in any order.
+ *  - Reading: nothing outside a file's text -- no other file's byte and no pad byte -- and
+ *    nothing behind the ']' of its ops region except its tail.
+ *  - Packing: as the other batched calls: lit_off[f] = the sum over g < f of lit_len[g] rounded
+ *    up to 16; *lit_need = lit_off[nfiles-1] + lit_len[nfiles-1].  The pad bytes and the bytes
+ *    behind *lit_need keep their values.
+ *  - Lengths and writing: lit_off, lit_len and *lit_need are always reported (computed on the
+ *    device).  The literal bytes are written only when d_lit != NULL and lit_buf_len >=
+ *    *lit_need; otherwise no byte is written and the call still returns SYDELTA_OK (size
+ *    query).  *out is filled in both cases (out == NULL: validate and size only); it is an
+ *    ordinary sydelta_delta_batch (sydelta_delta_batch_count / _get / _ptrs / _stats / _free;
+ *    sydelta_apply_delta_batch_device, sydelta_delta_batch_to_json_device).
+ *  - Refused texts (any spelling the single call refuses; a text shorter than the shortest
+ *    Delta is that file's refusal at byte 0, not a call error), file_status == NULL: the call
+ *    returns SYDELTA_E_INVAL, "file F: Delta JSON: not serde's compact form at byte P" for the
+ *    lowest refused file F, P the byte the single call names, measured inside that file's text;
+ *    *out stays NULL; nothing outside [0, *lit_need) of d_lit has been written, what lies inside
+ *    is unspecified.
+ *  - Refused texts, file_status != NULL: the call returns SYDELTA_OK; file_status[f] is 0 for a
+ *    parsed file, else 1 + P.  A refused file's delta in *out has no ops; its lit_len[f] is the
+ *    count the counting pass found (0 when its head or tail was refused) and it keeps its place
+ *    in the packing, so no second pass is needed; its bytes in d_lit are unspecified.  Every
+ *    other file is exactly as if it had been parsed alone.  Parse the refused ones with
+ *    sydelta_delta_from_json.
+ *  - Validation, on the host before a device is touched (SYDELTA_E_INVAL, the message names the
+ *    file where there is one): a NULL table with nfiles > 0, a NULL lit_need, a NULL d_text
+ *    with a non-empty text, a NULL d_lit with lit_buf_len > 0, a text that leaves the arena
+ *    (text_off[f] + text_len[f] > text_buf_len, overflow-checked: "file F: text [off, +len)
+ *    leaves its arena of N bytes"), more than 2^31 64-byte chunks of text in all.
+ *  - nfiles == 0 returns SYDELTA_OK with *lit_need = 0 and an empty batch without touching a
+ *    device.  A valid batch without a GPU is SYDELTA_E_NODEV.
+ *  - Stream order: the work is ordered on `stream` (NULL: the thread's library stream) and
+ *    complete when the call returns.  The host waits twice whatever the batch: for the per-file
+ *    counts (they size the op table and decide the literal arena), and at the end.  The numbers
+ *    of copies, allocations and launches do not depend on nfiles (an upload slot more per
+ *    20 480 files).  Ranks and positions are 64-bit: no 4 GiB limit.
+ *  - Staging: the file table reaches the device through two per-thread pinned slots of 640 KiB
+ *    (whatever the batch; released when the thread exits); the scratch (32 bytes per 64 bytes
+ *    of text, 96 bytes per file, 24 bytes per op) comes from the library's stream-ordered pool
+ *    and returns to it in stream order.  A batch is not split when memory is short: an
+ *    allocation failure is SYDELTA_E_OOM with the byte count. */
+int sydelta_delta_batch_from_json_device(int device,
+        const uint8_t *d_text, uint64_t text_buf_len, const uint64_t *text_off, const uint64_t *text_len,
+        uint64_t nfiles,
+        uint8_t *d_lit, uint64_t lit_buf_len,
+        uint64_t *lit_off /* nfiles, written */, uint64_t *lit_len /* nfiles, written */,
+        uint64_t *file_status /* nfiles, written; or NULL */,
+        uint64_t *lit_need, sydelta_delta_batch **out /* or NULL */, void *stream);
 /* The zstd frame (RFC 8878) of d_in[0, len) into d_out, on the device: what ssh.rs:1009-1017
  * sends (compress(delta_json, Compression::Zstd), compress/mod.rs:71-76) and sy-remote
  * decompresses (sy-remote.rs:160-179) -- typically the text of sydelta_delta_to_json_device.

@@ -1478,11 +1478,6 @@ void slab_close(OpSlab* sl) {
 }  // namespace
 
 
-struct sydelta_delta_batch {
-    std::vector<sydelta_delta> d;
-    sydelta_match_stats total{};
-};
-
 extern "C" int sydelta_expand_counters(uint64_t* device_files, uint64_t* host_batches) {
     if (device_files) *device_files = g_expand_files.load();
     if (host_batches) *host_batches = g_expand_host.load();

@@ -40,6 +40,10 @@ struct DArgs {
     const uint8_t* t;  // the whole text
     uint64_t e;        // end of the ops region (its ']')
     uint64_t nc;       // chunks of [kHead, e)
+    // The literal rank of the text's first literal.  0 for a text parsed alone; in a batch
+    // (sydelta_dparsebatch.hpp) the ranks run through all files, and a Data op's a = its
+    // rank - lbase indexes the file's own literal range.
+    uint64_t lbase = 0;
 };
 
 __host__ __device__ __forceinline__ bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
@@ -99,8 +103,9 @@ __host__ __device__ __forceinline__ bool op_follow(const DArgs& a, const T& t, u
 }
 
 // Chunk c's ops and literal bytes.  orank/lrank: exclusive scans (lrank with the total
-// at nc), pos: op starts by rank (nops entries).  Writes ops[rank] (kind, a = literal
-// offset or basis offset, b = size) and lit[rank] (lit NULL: checked only; L: a byte
+// at nc), pos: op starts by rank (nops: the rank behind the text's last op).  Writes
+// ops[rank] (kind, a = literal offset (rank - a.lbase) or basis offset, b = size) and
+// lit[rank] (lit NULL: checked only; L: a byte
 // pointer, or a type with operator bool and operator[](uint64_t) -> uint8_t&, the kernel's
 // LDS staging).  Returns the first bad position in the chunk or kNoBad.
 template <class T, class L = uint8_t*>
@@ -140,7 +145,7 @@ __host__ __device__ inline uint64_t chunk_parse(const DArgs& a, const T& t, uint
                 const uint64_t l0 = lits_before(a, a.t, lrank, q);
                 const uint64_t next = ork + 1 < nops ? pos[ork + 1] : a.e;
                 op.kind = SYDELTA_OP_DATA;
-                op.a = l0;
+                op.a = l0 - a.lbase;
                 op.b = lits_before(a, a.t, lrank, next) - l0;
             }
             ops[ork++] = op;

@@ -1,9 +1,9 @@
 // sydelta_host.hpp — host-side definitions shared by the C ABI translation units
 // (sydelta_api.cpp: signature / index / match / apply; sydelta_wire.cpp: wire formats; the
-// batch calls sydelta_applybatch.cpp, sydelta_jsonbatch.cpp, sydelta_zstdbatch.cpp and
-// sydelta_unzstdbatch.cpp; sydelta_unzstd_api.cpp, sydelta_blake3.cpp, sydelta_integrity.cpp,
-// sydelta_local.cpp).  The pinned staging ring of the calls that upload tables is
-// sydelta_stage.hpp, which stands alone.
+// batch calls sydelta_applybatch.cpp, sydelta_jsonbatch.cpp, sydelta_zstdbatch.cpp,
+// sydelta_unzstdbatch.cpp and sydelta_dparsebatch.cpp; sydelta_unzstd_api.cpp,
+// sydelta_blake3.cpp, sydelta_integrity.cpp, sydelta_local.cpp).  The pinned staging ring of
+// the calls that upload tables is sydelta_stage.hpp, which stands alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,6 +26,13 @@ struct sydelta_delta {
     sydelta_match_stats stats{};
     std::vector<uint8_t> lit;         // literal bytes (host-data entry points)
     std::vector<uint64_t> lit_off;    // per op: offset into lit, or UINT64_MAX
+};
+// One delta per file of a batched call (sydelta_match_batch_device and
+// sydelta_delta_pairs_device in sydelta_api.cpp, sydelta_delta_batch_from_json_device in
+// sydelta_dparsebatch.cpp); freed by sydelta_delta_batch_free.
+struct sydelta_delta_batch {
+    std::vector<sydelta_delta> d;
+    sydelta_match_stats total{};
 };
 
 namespace sydelta {

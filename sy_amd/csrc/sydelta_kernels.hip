@@ -18,6 +18,7 @@
 //
 // Launch wrappers at the bottom are the only symbols the host API uses.
 #include "sydelta_device.hpp"
+#include "sydelta_dparsebatch.hpp"
 #include "sydelta_internal.hpp"
 #include "sydelta_zstdbatch.hpp"
 
@@ -3755,12 +3756,13 @@ __device__ __forceinline__ LdsText dp_stage(const dparse::DArgs& a, uint64_t c0,
     return LdsText{a.t, (const lds_u8*)rows, p0, n};
 }
 
-__global__ __launch_bounds__(256) void k_dparse_count(dparse::DArgs a, uint64_t* __restrict__ ocnt,
-                                                      uint64_t* __restrict__ lcnt) {
-    __shared__ uint8_t st[4][kDpRows * kDpRow];
-    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) & ~63ull;  // the wave's first chunk
-    if (c0 >= a.nc) return;  // whole waves only
-    const LdsText t = dp_stage(a, c0, st[threadIdx.x >> 6]);
+// The wave bodies of the three kernels: the wave whose first chunk is c0 (c0 < a.nc, a multiple
+// of 64), `rows` its kDpRows * kDpRow bytes of LDS.  The single call's kernels (k_dparse_*) run
+// them over one text; the batched call's (k_dpb_*) over a tile of one file of a batch, with the
+// rank arrays at the file's place in the shared chunk table.
+__device__ __forceinline__ void dp_count_wave(const dparse::DArgs& a, uint64_t c0, uint8_t* rows,
+                                              uint64_t* __restrict__ ocnt, uint64_t* __restrict__ lcnt) {
+    const LdsText t = dp_stage(a, c0, rows);
     const uint64_t c = c0 + (threadIdx.x & 63);
     if (c >= a.nc) return;
     uint64_t no, nl;
@@ -3776,19 +3778,33 @@ __global__ __launch_bounds__(256) void k_dparse_count(dparse::DArgs a, uint64_t*
     lcnt[c] = nl;
 }
 
-__global__ __launch_bounds__(256) void k_dparse_place(dparse::DArgs a, const uint64_t* __restrict__ orank,
-                                                      uint64_t* __restrict__ pos) {
+__global__ __launch_bounds__(256) void k_dparse_count(dparse::DArgs a, uint64_t* __restrict__ ocnt,
+                                                      uint64_t* __restrict__ lcnt) {
     __shared__ uint8_t st[4][kDpRows * kDpRow];
-    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) & ~63ull;
-    if (c0 >= a.nc) return;
-    // a wave whose chunks start no op (a literal run's) has nothing to place: orank has nc + 1 entries
+    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) & ~63ull;  // the wave's first chunk
+    if (c0 >= a.nc) return;  // whole waves only
+    dp_count_wave(a, c0, st[threadIdx.x >> 6], ocnt, lcnt);
+}
+
+// orank: nc + 1 entries (the last: the rank behind the text's last op).
+__device__ __forceinline__ void dp_place_wave(const dparse::DArgs& a, uint64_t c0, uint8_t* rows,
+                                              const uint64_t* __restrict__ orank, uint64_t* __restrict__ pos) {
+    // a wave whose chunks start no op (a literal run's) has nothing to place
     if (orank[c0 + 64 < a.nc ? c0 + 64 : a.nc] == orank[c0]) return;  // wave-uniform
-    const LdsText t = dp_stage(a, c0, st[threadIdx.x >> 6]);
+    const LdsText t = dp_stage(a, c0, rows);
     const uint64_t c = c0 + (threadIdx.x & 63);
     if (c >= a.nc) return;
     DpFast f;
     dp_fast(a, t, c, f);
     if (!f.ok) dparse::chunk_place(a, t, c, orank[c], pos);
+}
+
+__global__ __launch_bounds__(256) void k_dparse_place(dparse::DArgs a, const uint64_t* __restrict__ orank,
+                                                      uint64_t* __restrict__ pos) {
+    __shared__ uint8_t st[4][kDpRows * kDpRow];
+    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) & ~63ull;
+    if (c0 >= a.nc) return;
+    dp_place_wave(a, c0, st[threadIdx.x >> 6], orank, pos);
 }
 
 // The literal bytes of a wave's chunks are one contiguous range of the output, [lrank[c0],
@@ -3806,16 +3822,14 @@ struct LdsLit {
     }
 };
 
-__global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t* __restrict__ orank,
-                                                const uint64_t* __restrict__ lrank, const uint64_t* __restrict__ pos,
-                                                uint64_t nops, sydelta_op* __restrict__ ops, uint8_t* lit,
-                                                unsigned long long* bad) {
-    __shared__ uint8_t st[4][kDpRows * kDpRow];
-    __shared__ uint8_t lo[4][kDpLitMax];
-    const uint32_t wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) & ~63ull;
-    if (c0 >= a.nc) return;
-    const LdsText t = dp_stage(a, c0, st[wid]);
+// slab: the wave's kDpLitMax bytes of LDS; nops: the rank behind the text's last op; lit: where
+// rank 0 of lrank's numbering goes (NULL: checked only); bad: the text's bad-word.
+__device__ __forceinline__ void dp_parse_wave(const dparse::DArgs& a, uint64_t c0, uint8_t* rows, uint8_t* slab,
+                                              const uint64_t* __restrict__ orank, const uint64_t* __restrict__ lrank,
+                                              const uint64_t* __restrict__ pos, uint64_t nops,
+                                              sydelta_op* __restrict__ ops, uint8_t* lit, unsigned long long* bad) {
+    const uint32_t lane = threadIdx.x & 63;
+    const LdsText t = dp_stage(a, c0, rows);
     const uint64_t c = c0 + lane;
     const uint64_t l0 = lrank[c0], l1 = lrank[c0 + 64 < a.nc ? c0 + 64 : a.nc];
     if (c < a.nc) {
@@ -3825,7 +3839,7 @@ __global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t*
         if (f.ok) {  // each literal's value; a leading zero or a value > 255 sends the chunk to the body
             f.ok = dparse::fast_values(f.x, f.lits, lrank[c], [&](uint64_t r, uint32_t v) {
                 if (lit) {
-                    if (staged) lo[wid][r - l0] = (uint8_t)v;
+                    if (staged) slab[r - l0] = (uint8_t)v;
                     else lit[r] = (uint8_t)v;
                 }
             });
@@ -3834,7 +3848,7 @@ __global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t*
             uint64_t b;
             if (staged)
                 b = dparse::chunk_parse(a, t, c, orank, lrank, pos, nops, ops,
-                                        LdsLit{(__attribute__((address_space(3))) uint8_t*)lo[wid], l0});
+                                        LdsLit{(__attribute__((address_space(3))) uint8_t*)slab, l0});
             else
                 b = dparse::chunk_parse(a, t, c, orank, lrank, pos, nops, ops, lit);
             if (b != dparse::kNoBad) atomicMin(bad, (unsigned long long)b);
@@ -3844,7 +3858,7 @@ __global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t*
     lds_fence();
     // [l0, l1): head bytes up to a dword boundary (of the absolute address), whole dwords,
     // tail bytes
-    const uint8_t* src = lo[wid];
+    const uint8_t* src = slab;
     uint64_t a0, a1;
     dparse::lit_split(l0, l1, (uint32_t)((uintptr_t)lit & 3), a0, a1);
     if (a0 >= a1) {
@@ -3859,6 +3873,101 @@ __global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t*
                            ((uint32_t)src[k + 3] << 24);
         *(uint32_t*)(lit + i) = v;
     }
+}
+
+__global__ __launch_bounds__(256) void k_dparse(dparse::DArgs a, const uint64_t* __restrict__ orank,
+                                                const uint64_t* __restrict__ lrank, const uint64_t* __restrict__ pos,
+                                                uint64_t nops, sydelta_op* __restrict__ ops, uint8_t* lit,
+                                                unsigned long long* bad) {
+    __shared__ uint8_t st[4][kDpRows * kDpRow];
+    __shared__ uint8_t lo[4][kDpLitMax];
+    const uint32_t wid = threadIdx.x >> 6;
+    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) & ~63ull;
+    if (c0 >= a.nc) return;
+    dp_parse_wave(a, c0, st[wid], lo[wid], orank, lrank, pos, nops, ops, lit, bad);
+}
+
+// K7db: the batched call (sydelta_dparsebatch.hpp).  The lane-per-file kernels, and the three
+// wave kernels over tiles: a wave takes tile blockIdx.x * 4 + its number, finds the tile's file
+// by bisection over the files' first tiles, and runs the wave body above on that file's text
+// with the rank arrays at the file's place in the shared chunk table.  A file that the tail
+// stage refused has no chunks (e = kHead), and the tiles past a file's last chunk (the grid is
+// bounded from the text's length, not its ops region) return at once.
+__global__ __launch_bounds__(dpb::kLanes) void k_dpb_tail(const uint8_t* __restrict__ text,
+                                                          const dpb::File* __restrict__ files, uint64_t nfiles,
+                                                          dpb::Rec* recs) {
+    const uint64_t f = (uint64_t)blockIdx.x * dpb::kLanes + threadIdx.x;
+    if (f >= nfiles) return;
+    recs[f] = dpb::tail_file(text, files[f]);
+}
+
+struct DpbTile {
+    dpb::File F;
+    dparse::DArgs a;
+    uint64_t f, c0;
+    bool live;
+};
+__device__ __forceinline__ DpbTile dpb_tile(const uint8_t* text, const dpb::File* files, uint64_t nfiles, uint64_t ntiles,
+                                            const dpb::Rec* recs, const uint64_t* lrank) {
+    DpbTile T{};
+    // the wave's number is the same in all its lanes: told so, the compiler keeps the tile, the
+    // bisection and the file's record in scalar registers, as the single call's arguments are
+    const uint64_t tile = (uint64_t)blockIdx.x * 4 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (tile >= ntiles) return T;
+    T.f = dpb::file_of_tile(files, nfiles, tile);
+    T.F = files[T.f];
+    T.c0 = (tile - T.F.tbase) * dpb::kTileChunks;
+    const dpb::Rec R = recs[T.f];
+    if (T.c0 >= dpb::chunks_of(R.e)) return T;
+    T.a = dpb::args_of(text, T.F, R, lrank ? lrank[T.F.cbase] : 0);
+    T.live = true;
+    return T;
+}
+
+__global__ __launch_bounds__(256) void k_dpb_count(const uint8_t* __restrict__ text, const dpb::File* __restrict__ files,
+                                                   uint64_t nfiles, uint64_t ntiles, const dpb::Rec* __restrict__ recs,
+                                                   uint64_t* __restrict__ ocnt, uint64_t* __restrict__ lcnt) {
+    __shared__ uint8_t st[4][kDpRows * kDpRow];
+    const DpbTile T = dpb_tile(text, files, nfiles, ntiles, recs, nullptr);
+    if (!T.live) return;
+    dp_count_wave(T.a, T.c0, st[threadIdx.x >> 6], ocnt + T.F.cbase, lcnt + T.F.cbase);
+}
+
+__global__ __launch_bounds__(dpb::kLanes) void k_dpb_sizes(const dpb::File* __restrict__ files, uint64_t nfiles,
+                                                           const uint64_t* __restrict__ orank,
+                                                           const uint64_t* __restrict__ lrank, dpb::Rec* recs,
+                                                           uint64_t* nops, uint64_t* lit_len, uint64_t* pad) {
+    const uint64_t f = (uint64_t)blockIdx.x * dpb::kLanes + threadIdx.x;
+    if (f >= nfiles) return;
+    uint64_t no, nl;
+    dpb::sizes_file(files[f], orank, lrank, recs[f], no, nl);
+    nops[f] = no;
+    lit_len[f] = nl;
+    pad[f] = dpb::pad16(nl);
+}
+
+__global__ __launch_bounds__(256) void k_dpb_place(const uint8_t* __restrict__ text, const dpb::File* __restrict__ files,
+                                                   uint64_t nfiles, uint64_t ntiles, const dpb::Rec* __restrict__ recs,
+                                                   const uint64_t* __restrict__ orank, uint64_t* __restrict__ pos) {
+    __shared__ uint8_t st[4][kDpRows * kDpRow];
+    const DpbTile T = dpb_tile(text, files, nfiles, ntiles, recs, nullptr);
+    if (!T.live) return;
+    dp_place_wave(T.a, T.c0, st[threadIdx.x >> 6], orank + T.F.cbase, pos);
+}
+
+__global__ __launch_bounds__(256) void k_dpb_parse(const uint8_t* __restrict__ text, const dpb::File* __restrict__ files,
+                                                   uint64_t nfiles, uint64_t ntiles, dpb::Rec* recs,
+                                                   const uint64_t* __restrict__ orank, const uint64_t* __restrict__ lrank,
+                                                   const uint64_t* __restrict__ lit_off, const uint64_t* __restrict__ pos,
+                                                   sydelta_op* __restrict__ ops, uint8_t* lit) {
+    __shared__ uint8_t st[4][kDpRows * kDpRow];
+    __shared__ uint8_t lo[4][kDpLitMax];
+    const uint32_t wid = threadIdx.x >> 6;
+    const DpbTile T = dpb_tile(text, files, nfiles, ntiles, recs, lrank);
+    if (!T.live) return;
+    const uint64_t* fo = orank + T.F.cbase;
+    dp_parse_wave(T.a, T.c0, st[wid], lo[wid], fo, lrank + T.F.cbase, pos, fo[T.a.nc], ops,
+                  dpb::lit_base(lit, lit_off[T.f], lrank[T.F.cbase]), (unsigned long long*)&recs[T.f].status);
 }
 
 __global__ __launch_bounds__(256) void k_json_len(const JsonPiece* __restrict__ pieces, uint64_t npieces,
@@ -5010,6 +5119,49 @@ hipError_t launch_dparse(const dparse::DArgs& a, const uint64_t* d_orank, const 
     ProfScope ps(prof, s, "k_dparse");
     hipLaunchKernelGGL(k_dparse, dim3(grid_for(a.nc, 256)), dim3(256), 0, s, a, d_orank, d_lrank, d_pos, nops, d_ops,
                        d_lit, d_bad);
+    return hipGetLastError();
+}
+
+// K7db (sydelta_dparsebatch.hpp).  The counts are zeroed first: the chunk table has room for
+// every chunk a text's length allows, and the chunks behind a file's ops region stay 0.
+hipError_t launch_dpb_count(const DpbArgs& a, hipStream_t s, Profiler* prof) {
+    const unsigned nf = (unsigned)((a.nfiles + dpb::kLanes - 1) / dpb::kLanes);
+    if ((a.ntiles + 3) / 4 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    {
+        ProfScope ps(prof, s, "k_dpb_tail");
+        hipLaunchKernelGGL(k_dpb_tail, dim3(nf), dim3(dpb::kLanes), 0, s, a.text, a.files, a.nfiles, a.recs);
+    }
+    // ocnt and lcnt lie back to back (sydelta_dparsebatch.cpp)
+    if (hipError_t e = hipMemsetAsync(a.ocnt, 0, 2 * (a.nchunks + 1) * 8, s)) return e;
+    if (a.ntiles) {
+        ProfScope ps(prof, s, "k_dpb_count");
+        hipLaunchKernelGGL(k_dpb_count, dim3(grid_for(a.ntiles, 4)), dim3(256), 0, s, a.text, a.files, a.nfiles, a.ntiles,
+                           a.recs, a.ocnt, a.lcnt);
+    }
+    if (hipError_t e = launch_exclusive_sum_u64(a.ocnt, a.orank, a.nchunks + 1, s)) return e;
+    if (hipError_t e = launch_exclusive_sum_u64(a.lcnt, a.lrank, a.nchunks + 1, s)) return e;
+    {
+        ProfScope ps(prof, s, "k_dpb_sizes");
+        hipLaunchKernelGGL(k_dpb_sizes, dim3(nf), dim3(dpb::kLanes), 0, s, a.files, a.nfiles, a.orank, a.lrank, a.recs,
+                           a.nops, a.lit_len, a.pad);
+    }
+    if (hipError_t e = launch_exclusive_sum_u64(a.pad, a.lit_off, a.nfiles, s)) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_dpb_parse(const DpbArgs& a, uint64_t* d_pos, sydelta_op* d_ops, uint8_t* d_lit, hipStream_t s,
+                            Profiler* prof) {
+    if (!a.ntiles) return hipSuccess;
+    {
+        ProfScope ps(prof, s, "k_dpb_place");
+        hipLaunchKernelGGL(k_dpb_place, dim3(grid_for(a.ntiles, 4)), dim3(256), 0, s, a.text, a.files, a.nfiles, a.ntiles,
+                           a.recs, a.orank, d_pos);
+    }
+    {
+        ProfScope ps(prof, s, "k_dpb_parse");
+        hipLaunchKernelGGL(k_dpb_parse, dim3(grid_for(a.ntiles, 4)), dim3(256), 0, s, a.text, a.files, a.nfiles, a.ntiles,
+                           a.recs, a.orank, a.lrank, a.lit_off, d_pos, d_ops, d_lit);
+    }
     return hipGetLastError();
 }
 

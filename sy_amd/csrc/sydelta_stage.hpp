@@ -1,5 +1,5 @@
 // sydelta_stage.hpp — the pinned staging ring of the calls that upload host tables in pieces
-// (sydelta_apply_delta_device and the four batch calls).  It includes only the HIP runtime API
+// (sydelta_apply_delta_device and the five batch calls).  It includes only the HIP runtime API
 // and the standard library, so a host program can include it alone (tests/csrc/stage_check.cpp
 // drives it against recording stand-ins of the HIP calls).
 //

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "sydelta_dparsebatch.hpp"  // tail_parse
 #include "sydelta_host.hpp"
 #include "sydelta_internal.hpp"
 
@@ -619,24 +620,6 @@ extern "C" int sydelta_checksums_from_json_device(const uint8_t* d_text, uint64_
 // tail (`],"source_size":N,"block_size":B}`) from two small copies; the device ranks and
 // parses the ops and literal bytes between them.  Data ops of the result index d_lit
 // (op.a = offset of its first literal byte), as sydelta_apply_delta_device reads them.
-namespace {
-// A u64 in serde's compact spelling at t[p, e): digits, no leading zero; returns the
-// digits consumed or 0.
-size_t host_dec(const char* t, size_t p, size_t e, uint64_t& v) {
-    uint64_t x = 0;
-    size_t k = 0;
-    while (p + k < e && t[p + k] >= '0' && t[p + k] <= '9') {
-        const uint64_t d = (uint64_t)(t[p + k] - '0');
-        if (x > (UINT64_MAX - d) / 10) return 0;
-        x = x * 10 + d;
-        ++k;
-    }
-    if (!k || (k > 1 && t[p] == '0')) return 0;
-    v = x;
-    return k;
-}
-}  // namespace
-
 extern "C" int sydelta_delta_from_json_device(const uint8_t* d_text, uint64_t len, uint8_t* d_lit, uint64_t lit_cap,
                                               uint64_t* lit_len, sydelta_delta** out, void* stream) try {
     if (!lit_len) return fail(SYDELTA_E_INVAL, "NULL argument");
@@ -645,36 +628,20 @@ extern "C" int sydelta_delta_from_json_device(const uint8_t* d_text, uint64_t le
     auto bad_at = [](uint64_t p) {
         return fail(SYDELTA_E_INVAL, "Delta JSON: not serde's compact form at byte %llu", (unsigned long long)p);
     };
-    static const char kTailKey[] = "],\"source_size\":";
-    // the shortest text: {"ops":[],"source_size":0,"block_size":0}
-    if (!d_text || len < dparse::kHead + (sizeof kTailKey - 1) + 17) return bad_at(0);
+    if (!d_text || len < dpb::kMinText) return bad_at(0);
     int dev = 0;
     (void)hipGetDevice(&dev);
     SYDELTA_ENTER_DEVICE(dev);
     hipStream_t s = call_stream(dev, stream);
-    // head and tail (the tail is < 80 bytes: two u64 and the keys)
-    char head[dparse::kHead], tail[96];
+    // head and tail, parsed by the body the batched call runs per file (dpb::tail_parse)
+    uint8_t head[dparse::kHead], tail[dpb::kTailMax];
     const uint64_t tl = std::min<uint64_t>(len - dparse::kHead, sizeof tail);
     HIP_TRY(hipMemcpyAsync(head, d_text, dparse::kHead, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(tail, d_text + len - tl, tl, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (memcmp(head, "{\"ops\":[", dparse::kHead) != 0) return bad_at(0);
-    size_t at = SIZE_MAX;  // the last "],\"source_size\":" in the tail
-    for (size_t i = 0; i + sizeof kTailKey - 1 <= tl; ++i)
-        if (memcmp(tail + i, kTailKey, sizeof kTailKey - 1) == 0) at = i;
-    if (at == SIZE_MAX) return bad_at(len - tl);
-    uint64_t src_size = 0, blk = 0;
-    size_t q = at + sizeof kTailKey - 1, k;
-    static const char kBs[] = ",\"block_size\":";
-    if (!(k = host_dec(tail, q, tl, src_size))) return bad_at(len - tl + q);
-    q += k;
-    if (tl - q < sizeof kBs - 1 || memcmp(tail + q, kBs, sizeof kBs - 1) != 0) return bad_at(len - tl + q);
-    q += sizeof kBs - 1;
-    if (!(k = host_dec(tail, q, tl, blk))) return bad_at(len - tl + q);
-    q += k;
-    if (!(q + 1 == tl && tail[q] == '}')) return bad_at(len - tl + q);
-    const uint64_t E = len - tl + at;  // the ops array's ']'
-    if (E < dparse::kHead) return bad_at(E);
+    const dpb::Rec rec = dpb::tail_parse(head, tail, len, tl);
+    if (rec.status != dpb::kNoBad) return bad_at(rec.status);
+    const uint64_t E = rec.e, src_size = rec.n, blk = rec.b;  // E: the ops array's ']'
     dparse::DArgs a{d_text, E, (E - dparse::kHead + dparse::kChunk - 1) / dparse::kChunk};
     uint64_t nops = 0, nlit = 0;
     CallProf cp;

@@ -471,6 +471,26 @@ def apply_wire(basis: torch.Tensor, payload: torch.Tensor, stream=None):
     return apply_device(basis, delta, lit, stream=stream)
 
 
+def apply_wire_batch(basis: torch.Tensor, boffs, blens, frames: torch.Tensor, foffs, flens,
+                     out: torch.Tensor | None = None, ooffs=None, stream=None):
+    """sy-remote apply-delta (sy-remote.rs:153-179) for a whole batch of payloads in HBM, the
+    receiver's loop closed: the frames decoded (wire_batch_to_text), the Delta texts parsed
+    (wire.delta_batch_from_json_device) and the deltas applied (apply_batch), each step one call
+    (with its size query) for any number of files; no text leaves the device.  File f's payload
+    is frames[foffs[f] : foffs[f] + flens[f]], a zstd frame as delta_batch_to_wire writes them;
+    its basis is basis[boffs[f] : boffs[f] + blens[f]].  `out` and `ooffs` as for apply_batch.
+    Returns (out, ooffs, per_file_stats).  A frame the device decoder refuses, or a text that is
+    not in the compact form, raises SyDeltaError naming the file."""
+    from . import wire
+
+    text, toffs, tlens = wire_batch_to_text(frames, foffs, flens, stream=stream)
+    deltas, lit, loffs, llens = wire.delta_batch_from_json_device(text, toffs, tlens, stream=stream)
+    try:
+        return apply_batch(basis, boffs, blens, deltas, lit, loffs, llens, out=out, ooffs=ooffs, stream=stream)
+    finally:
+        deltas.close()
+
+
 def block_compare(src: torch.Tensor, dst: torch.Tensor, block_size: int, stream=None):
     """The local transport's block-compare loop (local.rs:541-619) on device bytes.
     Returns (changed uint8 tensor with one flag per source block, stats dict with

@@ -219,6 +219,55 @@ def delta_from_json_device(d_text, stream=None):
         lib.sydelta_delta_free(h)
 
 
+def delta_batch_from_json_device(text, toffs, tlens, lit=None, refused_ok=False, stream=None):
+    """The Delta texts of a whole batch parsed on the device in one call
+    (sydelta_delta_batch_from_json_device): file f's text is text[toffs[f] : toffs[f] +
+    tlens[f]] (a uint8 device tensor and tables of any alignment and order: what
+    zstd_decompress_batch_device returns), its delta what delta_from_json_device gives for that
+    text alone.  The literal bytes are packed into `lit` in file order, each file's at a
+    multiple of 16; with lit=None the sizes are asked for first and an arena of that size is
+    allocated, so the parse runs twice: a caller that knows a bound passes `lit` for a single
+    call.  Returns (DeltaBatch, lit, loffs, llens): file f's Data ops index lit[loffs[f] :
+    loffs[f] + llens[f]], which is what device.apply_batch takes.
+
+    A text in any other spelling raises SyDeltaError (SYDELTA_E_INVAL, "file F: Delta JSON: not
+    serde's compact form at byte P").  With refused_ok=True the call succeeds instead and
+    returns (DeltaBatch, lit, loffs, llens, status): status[f] is 0 for a parsed file, else
+    1 + P; such a file's delta has no ops, and its text is for delta_from_json."""
+    import torch
+
+    from .device import DeltaBatch, _ptr, _stream
+
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (toffs, tlens)]
+    n = len(arrs[0])
+    if len(arrs[1]) != n:
+        raise ValueError("offset and length tables differ in length")
+    loffs = np.zeros(n, dtype=np.uint64)
+    llens = np.zeros(n, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint64) if refused_ok else None
+    need = ctypes.c_uint64()
+    tp = _ptr(text) if text.numel() else None
+
+    def call(o, h):
+        check(lib.sydelta_delta_batch_from_json_device(
+            text.device.index or 0, tp, text.numel(), arrs[0].ctypes.data, arrs[1].ctypes.data, n,
+            _ptr(o) if o is not None and o.numel() else None, o.numel() if o is not None else 0, loffs.ctypes.data,
+            llens.ctypes.data, status.ctypes.data if refused_ok else None, ctypes.byref(need),
+            ctypes.byref(h) if h is not None else None, _stream(stream)))
+
+    if lit is None:
+        call(None, None)
+        lit = torch.empty(max(1, need.value), dtype=torch.uint8, device=text.device)
+    h = ctypes.c_void_p()
+    call(lit, h)
+    batch = DeltaBatch(h)
+    if need.value > lit.numel():
+        batch.close()
+        raise _lib.SyDeltaError(_lib.SYDELTA_E_INVAL, f"the batch's literals need {need.value} bytes, lit holds {lit.numel()}")
+    res = (batch, lit[:need.value], loffs, llens)
+    return res + (status,) if refused_ok else res
+
+
 def zstd_compress_device(d_text, stream=None, device: int | None = None):
     """zstd frame (Huffman literals, FSE-coded sequences) of the bytes of a uint8 device tensor, as a uint8
     device tensor: the compression ssh.rs:1009-1017 applies to the Delta JSON.  The
