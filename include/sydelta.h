@@ -487,6 +487,109 @@ int sydelta_checksums_to_json_device(const uint32_t *d_weak, const uint64_t *d_s
  * sydelta_checksums_from_json. */
 int sydelta_checksums_from_json_device(const uint8_t *d_text, uint64_t len, sydelta_block_checksum *d_out,
                                        uint64_t cap, uint64_t *n_out, void *stream);
+/* `sy-remote checksums` (sy-remote.rs:145-147) for nfiles signatures in one call: the receiver's
+ * step behind sydelta_signature_batch_device.
+ * File f: its text is byte for byte what sydelta_checksums_to_json_device writes for
+ *         (d_weak + S_f, d_strong + S_f, nblocks[f], block_size, last_size[f]), S_f = the sum of
+ *         nblocks[g] over g < f; it goes to d_out[text_off[f], +text_len[f]).  A file without
+ *         blocks is "[]" (its last_size is not read).  The texts exclude println!'s newline.
+ *  - Inputs: d_weak / d_strong are the concatenated SoA in file order that
+ *    sydelta_signature_batch_device writes and sydelta_index_create_batch reads; nblocks,
+ *    last_size, text_off and text_len are host arrays of nfiles entries.
+ *  - Packing: as sydelta_delta_batch_to_json_device: text_off[f] = the sum over g < f of
+ *    text_len[g] rounded up to 16; *out_need = text_off[nfiles-1] + text_len[nfiles-1].
+ *  - Lengths and writing: text_off, text_len and *out_need are always reported (computed on the
+ *    device from the values).  The texts are written only when d_out != NULL and out_buf_len >=
+ *    *out_need; otherwise no byte is written and the call still returns SYDELTA_OK (size query).
+ *    sydelta_checksums_batch_to_json_bound gives an arena size that always suffices, so one call
+ *    does.  After the wait every text_len[f] is checked against the bounds its implied fields
+ *    give; a length outside them is SYDELTA_E_KERNEL, as in the single call.
+ *  - Writing: nothing outside [text_off[f], text_off[f] + text_len[f]); the pad bytes keep their
+ *    values.  d_out may have any alignment: 16-byte stores are phased on the absolute address
+ *    and the partial granules at a tile's two ends are written byte by byte.  Every '[', ']' and
+ *    "[]" is written by the kernels.
+ *  - Validation, on the host before a device is touched (SYDELTA_E_INVAL, "file F: ..." where
+ *    there is a file): a NULL table with nfiles > 0, a NULL out_need, a NULL d_weak / d_strong
+ *    while the batch has entries, block_size 0 or above 2^32, last_size[f] outside
+ *    (0, block_size] for a file with blocks, offsets (nblocks[f]-1) * block_size + last_size[f]
+ *    that overflow, a sum of nblocks that overflows, more than 2^31 tiles of 256 blocks.
+ *  - nfiles == 0 returns SYDELTA_OK with *out_need = 0 without touching a device.  A valid batch
+ *    without a GPU is SYDELTA_E_NODEV.
+ *  - Stream order: the work is ordered on `stream` (NULL: the thread's library stream) and
+ *    complete when the call returns.  The host waits once, at the end (whether the arena holds
+ *    the texts is decided on the device).  The numbers of copies, allocations and launches do
+ *    not depend on nfiles (an upload slot more per 20 480 files).
+ *  - Staging: the file table reaches the device through two per-thread pinned slots of 640 KiB
+ *    (whatever the batch; released when the thread exits); the scratch (56 bytes per file, 16
+ *    per 256 blocks) comes from the library's stream-ordered pool and returns to it in stream
+ *    order.  A batch is never split: an allocation failure is SYDELTA_E_OOM with the byte count. */
+int sydelta_checksums_batch_to_json_device(int device,
+        const uint32_t *d_weak, const uint64_t *d_strong,          /* concatenated SoA, file order */
+        const uint64_t *nblocks, const uint64_t *last_size,        /* host, nfiles */
+        uint64_t nfiles, uint64_t block_size,
+        uint8_t *d_out, uint64_t out_buf_len,
+        uint64_t *text_off /* nfiles, written */, uint64_t *text_len /* nfiles, written */,
+        uint64_t *out_need, void *stream);
+/* Upper bound of *out_need above from the implied fields alone (weak 10 digits, strong 20; host
+ * only, no device): UINT64_MAX on a NULL table, a block_size out of range or overflow. */
+uint64_t sydelta_checksums_batch_to_json_bound(const uint64_t *nblocks, const uint64_t *last_size,
+        uint64_t nfiles, uint64_t block_size);
+/* The sender's parse of `sy-remote checksums`' line (ssh.rs:967-973) for nfiles texts in one
+ * call, straight into the tables sydelta_index_create_batch takes.
+ * File f: its text d_text[text_off[f], +text_len[f]) is parsed by the grammar of
+ *         sydelta_checksums_from_json_device (the same accepted spellings, the same first bad
+ *         byte, measured inside the file's text) and held to the layout compute_checksums
+ *         (checksum.rs:46-76) produces for block_size, which the sender chose itself
+ *         (ssh.rs:951-960): entry i has index == i, offset == i * block_size and size ==
+ *         block_size, except the last entry, whose size lies in (0, block_size].  A real
+ *         sy-remote always writes this layout.  Its values go to d_weak / d_strong
+ *         [sig_off[f] + i], nblocks[f] is its entry count and last_size[f] its last entry's size
+ *         (0 for "[]").
+ *  - Output: sig_off[f] = the sum of nblocks[g] over g < f; *sig_need = the sum of all nblocks:
+ *    the concatenated SoA in file order, as sydelta_signature_batch_device writes it.
+ *  - Size query: sig_off, nblocks, last_size and *sig_need are always reported.  The values are
+ *    written only when d_weak and d_strong are non-NULL and sig_cap >= *sig_need (entries);
+ *    otherwise nothing is written and the call still returns SYDELTA_OK.
+ *  - Refused files, file_status == NULL: the call returns SYDELTA_E_INVAL for the lowest refused
+ *    file F, "file F: checksum JSON: not serde's compact form at byte P" or "file F: checksum
+ *    JSON: entry at byte P is not block I of a signature with block size B" (P: the entry's
+ *    '{').  The tables are filled; the SoA is unspecified.
+ *  - Refused files, file_status != NULL: the call returns SYDELTA_OK; file_status[f] is 0 for a
+ *    parsed file, 1 + P for a spelling refusal and (1 << 63) | (1 + P) for a layout refusal; a
+ *    file with both kinds reports the spelling one.  A text shorter than 2 bytes is that file's
+ *    refusal at byte 0, not a call error.  A refused file keeps its place: nblocks[f] is the
+ *    number of '{' the counting pass found, so sig_off of the files behind it is final and no
+ *    second pass is needed; its slots of the SoA are unspecified and its last_size is block_size
+ *    (0 without a '{'), which sydelta_index_create_batch takes.  Build the
+ *    batch index with the tables as returned and discard that file's delta (a batched match
+ *    treats files independently, so every other file is exactly as if it had been parsed
+ *    alone); handle the refused file on the host with sydelta_checksums_from_json +
+ *    sydelta_generate_delta_buf.
+ *  - Reading: nothing outside a file's text beyond the 16-byte granules holding its first and
+ *    last byte (Conventions, "Data layout in HBM"); no result depends on a byte outside the
+ *    text, pads included.  Texts may overlap, repeat or come in any order, at any alignment.
+ *  - Validation, on the host before a device is touched (SYDELTA_E_INVAL, "file F: ..." where
+ *    there is a file): a NULL table with nfiles > 0, a NULL sig_need, a NULL d_text with a
+ *    non-empty text, a text that leaves the arena ("file F: text [off, +len) leaves its arena of
+ *    N bytes"), block_size 0 or above 2^32, more than 2^31 64-byte chunks of text in all.
+ *  - nfiles == 0 returns SYDELTA_OK with *sig_need = 0 without touching a device.  A valid batch
+ *    without a GPU is SYDELTA_E_NODEV.
+ *  - Stream order: the work is ordered on `stream` (NULL: the thread's library stream) and
+ *    complete when the call returns.  The host waits once, at the end (whether the SoA holds the
+ *    entries is decided on the device).  The numbers of copies, allocations and launches do not
+ *    depend on nfiles (an upload slot more per 20 480 files).
+ *  - Staging: the file table reaches the device through two per-thread pinned slots of 640 KiB;
+ *    the scratch (16 bytes per 64 bytes of text, 72 bytes per file) comes from the library's
+ *    stream-ordered pool and returns to it in stream order.  A batch is never split: an
+ *    allocation failure is SYDELTA_E_OOM with the byte count. */
+int sydelta_checksums_batch_from_json_device(int device,
+        const uint8_t *d_text, uint64_t text_buf_len, const uint64_t *text_off, const uint64_t *text_len,
+        uint64_t nfiles, uint64_t block_size,
+        uint32_t *d_weak, uint64_t *d_strong, uint64_t sig_cap,    /* entries; SoA out */
+        uint64_t *sig_off /* nfiles, written */, uint64_t *nblocks /* nfiles, written */,
+        uint64_t *last_size /* nfiles, written */,
+        uint64_t *file_status /* nfiles, written; or NULL */,
+        uint64_t *sig_need, void *stream);
 /* serde_json::from_str::<Delta> (sy-remote.rs:175) on the device, for text in HBM in the
  * compact form the sender writes (serde_json::to_string, ssh.rs:1003).  *lit_len = the
  * delta's literal bytes; with d_lit (device, lit_cap >= *lit_len) they are written there

@@ -122,6 +122,11 @@ SIGNATURES = [
     ("sydelta_delta_from_json", _i, [_vp, _u64, _pp]),
     ("sydelta_checksums_to_json_device", _i, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
     ("sydelta_checksums_from_json_device", _i, [_vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
+    ("sydelta_checksums_batch_to_json_bound", _u64, [_vp, _vp, _u64, _u64]),
+    ("sydelta_checksums_batch_to_json_device", _i, [_i, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp,
+                                                    ctypes.POINTER(_u64), _vp]),
+    ("sydelta_checksums_batch_from_json_device", _i, [_i, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp,
+                                                      _vp, _vp, ctypes.POINTER(_u64), _vp]),
     ("sydelta_delta_from_json_device", _i, [_vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _pp, _vp]),
     ("sydelta_delta_batch_from_json_device", _i, [_i, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp,
                                                   ctypes.POINTER(_u64), _pp, _vp]),
@@ -177,13 +182,14 @@ def _load() -> ctypes.CDLL:
             # decoder, the batched apply, the batched Delta JSON writer and parser and the batched
             # zstd compressor live in translation units of their own (sydelta_blake3.cpp,
             # sydelta_unzstd_api.cpp, sydelta_applybatch.cpp, sydelta_jsonbatch.cpp,
-            # sydelta_zstdbatch.cpp, sydelta_unzstdbatch.cpp, sydelta_dparsebatch.cpp); a library built from the
+            # sydelta_zstdbatch.cpp, sydelta_unzstdbatch.cpp, sydelta_dparsebatch.cpp), and so do the
+            # batched signature JSON writer and parser (sydelta_sigbatch.cpp); a library built from the
             # other host units alone (the emulated-device build of the host-logic tests, loaded
             # through this table from another path) has none of them, and calling one there
             # raises AttributeError.
             if name.startswith(("sydelta_blake3_", "sydelta_zstd_decompress_", "sydelta_apply_delta_batch_",
                                 "sydelta_delta_batch_to_json_", "sydelta_delta_batch_from_json_", "sydelta_zstd_batch_",
-                                "sydelta_zstd_compress_batch_")) and \
+                                "sydelta_zstd_compress_batch_", "sydelta_checksums_batch_")) and \
                     LIB_PATH != os.path.join(HERE, "libsydelta.so"):
                 continue
             raise ImportError(f"{LIB_PATH} does not export {name}")

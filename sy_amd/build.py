@@ -17,7 +17,7 @@ SOURCES = ["sydelta_kernels.hip", "sydelta_filewalk.hip", "sydelta_api.cpp", "sy
            "sydelta_blake3.hip", "sydelta_blake3.cpp", "sydelta_unzstd.hip", "sydelta_unzstd_api.cpp",
            "sydelta_applybatch.hip", "sydelta_applybatch.cpp", "sydelta_jsonbatch.hip", "sydelta_jsonbatch.cpp",
            "sydelta_zstdbatch.hip", "sydelta_zstdbatch.cpp", "sydelta_unzstdbatch.hip", "sydelta_unzstdbatch.cpp",
-           "sydelta_dparsebatch.cpp"]
+           "sydelta_dparsebatch.cpp", "sydelta_sigbatch.hip", "sydelta_sigbatch.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "sydelta.h")]
 # objects stay in build/obj (the host sanitizer test links sydelta_kernels.o)
 OBJDIR = os.path.join(ROOT, "build", "obj")

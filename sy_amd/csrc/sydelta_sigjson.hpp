@@ -160,7 +160,9 @@ __host__ __device__ inline bool get_lit(const T& t, uint64_t len, uint64_t& p, c
 
 // The entry whose '{' is at t[p], in exactly the compact form, with the right characters
 // before and after it; fills r.  False otherwise.
-__host__ __device__ inline bool parse_entry(const uint8_t* t, uint64_t len, uint64_t p, sydelta_block_checksum& r) {
+// T: as get_dec's (the batched parser's waves read their tile from LDS, sydelta_sigbatch.hip).
+template <class T>
+__host__ __device__ inline bool parse_entry(const T& t, uint64_t len, uint64_t p, sydelta_block_checksum& r) {
     if (!(p == 1 ? t[0] == '[' : p >= 2 && t[p - 1] == ',' && t[p - 2] == '}')) return false;
     uint64_t q = p, v = 0;
     uint32_t k;
@@ -185,7 +187,8 @@ __host__ __device__ inline bool parse_entry(const uint8_t* t, uint64_t len, uint
 }
 
 // '{' in chunk c of the text.
-__host__ __device__ inline uint32_t chunk_entries(const uint8_t* t, uint64_t len, uint64_t c) {
+template <class T>
+__host__ __device__ inline uint32_t chunk_entries(const T& t, uint64_t len, uint64_t c) {
     uint32_t m = 0;
     for (uint64_t p = c * kParseChunk; p < len && p < (c + 1) * kParseChunk; ++p) m += t[p] == '{';
     return m;
@@ -194,7 +197,8 @@ __host__ __device__ inline uint32_t chunk_entries(const uint8_t* t, uint64_t len
 // Chunk c's entries, ranked from rank: parsed into out[rank..] (out NULL or past cap:
 // checked only); returns the first bad position in the chunk or UINT64_MAX.  Chunk 0
 // also checks the head: "[]" or "[{".
-__host__ __device__ inline uint64_t chunk_parse(const uint8_t* t, uint64_t len, uint64_t c, uint64_t rank,
+template <class T>
+__host__ __device__ inline uint64_t chunk_parse(const T& t, uint64_t len, uint64_t c, uint64_t rank,
                                                sydelta_block_checksum* out, uint64_t cap) {
     if (c == 0 && !(len >= 2 && t[0] == '[' && (len == 2 ? t[1] == ']' : t[1] == '{'))) return 0;
     for (uint64_t p = c * kParseChunk; p < len && p < (c + 1) * kParseChunk; ++p) {
@@ -205,6 +209,12 @@ __host__ __device__ inline uint64_t chunk_parse(const uint8_t* t, uint64_t len, 
         ++rank;
     }
     return UINT64_MAX;
+}
+
+// chunk_parse's head check, for a parser with a chunk body of its own (sydelta_sigbatch.hpp).
+template <class T>
+__host__ __device__ inline bool head_ok(const T& t, uint64_t len) {
+    return len >= 2 && t[0] == '[' && (len == 2 ? t[1] == ']' : t[1] == '{');
 }
 
 // sum_{i < n} digits(i * m), in O(20): digits(v) = 1 + #{d >= 1 : v >= 10^d}, and

@@ -451,6 +451,40 @@ def wire_batch_to_text(frames: torch.Tensor, foffs, flens, out: torch.Tensor | N
     return wire.zstd_decompress_batch_device(frames, foffs, flens, out=out, refused_ok=refused_ok, stream=stream)
 
 
+def _sig_tables(lens, block_size: int):
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    bs = np.uint64(block_size)
+    nblocks = (lens + (bs - np.uint64(1))) // bs
+    last = np.where(nblocks > 0, lens - (np.maximum(nblocks, np.uint64(1)) - np.uint64(1)) * bs, 0).astype(np.uint64)
+    return nblocks, last
+
+
+def signature_batch_text(buf: torch.Tensor, offs, lens, block_size: int, stream=None):
+    """`sy-remote checksums` (sy-remote.rs:145-147) for a whole batch of files in HBM, the
+    receiver's answer in two calls for any number of files: the signatures (signature_batch),
+    then their texts (wire.checksums_batch_to_json_device).  Returns (text, toffs, tlens): file
+    f's line, without its newline, is text[toffs[f] : toffs[f] + tlens[f]]."""
+    from . import wire
+
+    weak, strong = signature_batch(buf, offs, lens, block_size, stream=stream)
+    nblocks, last = _sig_tables(lens, block_size)
+    return wire.checksums_batch_to_json_device(weak, strong, nblocks, last, block_size, stream=stream)
+
+
+def batch_index_from_text(text: torch.Tensor, toffs, tlens, block_size: int, refused_ok: bool = False, stream=None):
+    """The sender's side of the same exchange (ssh.rs:967-973, generator.rs:75-81) for a whole
+    batch: the texts parsed into the concatenated SoA (wire.checksums_batch_from_json_device)
+    and the per-file probe tables built from it, two calls for any number of files.  Returns a
+    BatchIndex for match_batch, and with refused_ok (BatchIndex, status): a refused file keeps
+    its place in the index, its delta is to be discarded and its text parsed on the host."""
+    from . import wire
+
+    res = wire.checksums_batch_from_json_device(text, toffs, tlens, block_size, refused_ok=refused_ok, stream=stream)
+    weak, strong, nblocks, last = res[:4]
+    ix = BatchIndex(weak, strong, nblocks, last, block_size, device=text.device.index or 0, stream=stream)
+    return (ix, res[4]) if refused_ok else ix
+
+
 ZSTD_MAGIC = bytes([0x28, 0xB5, 0x2F, 0xFD])
 
 

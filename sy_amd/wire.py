@@ -194,6 +194,91 @@ def checksums_from_json_device(d_text, stream=None):
     return out[:n.value * _SIG_DTYPE.itemsize], n.value
 
 
+def checksums_batch_to_json_device(weak, strong, nblocks, last_sizes, block_size: int, out=None, stream=None):
+    """The signature texts of a whole batch written on the device in one call
+    (sydelta_checksums_batch_to_json_device): weak / strong are the concatenated SoA in file
+    order (device.signature_batch), file f's text is checksums_to_json_device's of its
+    nblocks[f] entries with last_sizes[f] ("[]" for a file without blocks).  The texts are
+    packed into `out` in file order, each starting on a multiple of 16; with out=None an arena
+    of sydelta_checksums_batch_to_json_bound bytes is allocated, so one call does.
+    Returns (out trimmed to the packed size, toffs, tlens).  Raises SyDeltaError
+    (SYDELTA_E_INVAL) when a given `out` does not hold the texts: nothing was written."""
+    import torch
+
+    from .device import _ptr, _stream
+
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (nblocks, last_sizes)]
+    n = len(arrs[0])
+    if len(arrs[1]) != n:
+        raise ValueError("nblocks and last_sizes differ in length")
+    if strong.numel() != weak.numel():
+        raise ValueError("weak and strong arrays differ in length")
+    if n and weak.numel() < sum(int(x) for x in arrs[0]):
+        raise ValueError("the SoA holds fewer entries than nblocks sums to")
+    if out is None:
+        bound = int(lib.sydelta_checksums_batch_to_json_bound(arrs[0].ctypes.data, arrs[1].ctypes.data, n, block_size))
+        if bound == 0xFFFFFFFFFFFFFFFF:
+            raise ValueError("no bound for the batch's text (a block size out of range or a size that overflows)")
+        out = torch.empty(max(bound, 1), dtype=torch.uint8, device=weak.device)
+    toffs = np.zeros(n, dtype=np.uint64)
+    tlens = np.zeros(n, dtype=np.uint64)
+    need = ctypes.c_uint64()
+    have = weak.numel() > 0
+    check(lib.sydelta_checksums_batch_to_json_device(
+        weak.device.index or 0, _ptr(weak) if have else None, _ptr(strong) if have else None, arrs[0].ctypes.data,
+        arrs[1].ctypes.data, n, block_size, _ptr(out), out.numel(), toffs.ctypes.data, tlens.ctypes.data,
+        ctypes.byref(need), _stream(stream)))
+    if need.value > out.numel():
+        raise _lib.SyDeltaError(_lib.SYDELTA_E_INVAL, f"the batch's text needs {need.value} bytes, out holds {out.numel()}")
+    return out[:need.value], toffs, tlens
+
+
+def checksums_batch_from_json_device(text, toffs, tlens, block_size: int, refused_ok=False, stream=None):
+    """The signature texts of a whole batch parsed on the device in one call
+    (sydelta_checksums_batch_from_json_device): file f's text is text[toffs[f] : toffs[f] +
+    tlens[f]] (a uint8 device tensor and tables of any alignment and order), parsed by
+    checksums_from_json_device's grammar and held to the layout of a signature with
+    `block_size`.  Returns (weak, strong, nblocks, last_sizes): the concatenated SoA in file
+    order (int32 / int64 device tensors holding the u32 / u64 bit patterns, as
+    device.signature_batch returns them) and its tables, which is what device.BatchIndex takes.
+    The SoA is sized from the text (one entry per 50 bytes at the most), so one call does.
+
+    A refused text raises SyDeltaError (SYDELTA_E_INVAL, "file F: checksum JSON: ...").  With
+    refused_ok=True the call succeeds instead and returns (weak, strong, nblocks, last_sizes,
+    status): status[f] is 0 for a parsed file, 1 + P for a spelling refusal at byte P and
+    (1 << 63) | (1 + P) for an entry at byte P that is not in the layout; such a file keeps its
+    place in the SoA (its slots unspecified) and its text is for checksums_from_json."""
+    import torch
+
+    from .device import _ptr, _stream
+
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (toffs, tlens)]
+    n = len(arrs[0])
+    if len(arrs[1]) != n:
+        raise ValueError("offset and length tables differ in length")
+    # the shortest entry, [{"index":0,"offset":0,"size":1,"weak":0,"strong":0}, is 52 bytes; only
+    # a refused text can count more '{' than that, and then the call is repeated with room
+    cap = int((arrs[1] // np.uint64(50) + np.uint64(1)).sum()) if n else 0
+    soffs = np.zeros(n, dtype=np.uint64)
+    nblocks = np.zeros(n, dtype=np.uint64)
+    lasts = np.zeros(n, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint64) if refused_ok else None
+    need = ctypes.c_uint64()
+    for _ in range(2):
+        weak = torch.empty(max(1, cap), dtype=torch.int32, device=text.device)
+        strong = torch.empty(max(1, cap), dtype=torch.int64, device=text.device)
+        check(lib.sydelta_checksums_batch_from_json_device(
+            text.device.index or 0, _ptr(text) if text.numel() else None, text.numel(), arrs[0].ctypes.data,
+            arrs[1].ctypes.data, n, block_size, _ptr(weak), _ptr(strong), weak.numel(), soffs.ctypes.data,
+            nblocks.ctypes.data, lasts.ctypes.data, status.ctypes.data if refused_ok else None, ctypes.byref(need),
+            _stream(stream)))
+        if need.value <= weak.numel():
+            break
+        cap = need.value
+    res = (weak[:need.value], strong[:need.value], nblocks, lasts)
+    return res + (status,) if refused_ok else res
+
+
 def delta_from_json_device(d_text, stream=None):
     """serde_json::from_str::<Delta> of a compact Delta JSON text in HBM (uint8 device
     tensor) parsed on the device: returns (ops as [(kind, a, b)] with Data ops indexing the
