@@ -681,6 +681,11 @@ struct sydelta_index {
     // another path (index_full): a C4 step then has no index build at all.
     bool deferred = false;
     std::mutex build_mu;
+    // One file from device arrays takes the collision build (DeviceIndex::coll), which may
+    // overflow: until the first index_wait has read its flag (coll_pin: mapped, the build sets
+    // it) no kernel that reads the tables is queued.  Guarded by build_mu.
+    bool coll_pending = false;
+    PinnedHits coll_pin;
     // A single-file index's scan extras (the level-1 filter, the fat table) are filled by the
     // first scan that runs against it (scan_index): the chunk walk and the aligned probe read
     // only the Bloom filter and the exact table (C5: 1-8 Mi keys).  extras_ev orders scans on
@@ -691,16 +696,43 @@ struct sydelta_index {
 };
 
 namespace {
-// Order `s` after the index build (a no-op for an index built synchronously).
-hipError_t index_wait(const sydelta_index* x, hipStream_t s) {
+// index_wait with build_mu held.  An index whose collision build has not been looked at
+// (coll_pending) is settled first: the host waits for the build and reads its overflow flag,
+// and a build that overflowed is repeated on `s` with the sort (`ready` recorded again).
+hipError_t index_wait_locked(sydelta_index* x, hipStream_t s) {
+    if (x->coll_pending) {
+        // polled: the thread goes on to queue the kernels on the step's critical path
+        hipError_t q;
+        while ((q = hipEventQuery(x->ready)) == hipErrorNotReady) _mm_pause();
+        (void)hipGetLastError();  // (a query that found the event pending is no error to report later)
+        if (q != hipSuccess) return q;
+        const bool over = x->ix.coll_flag && *(volatile uint32_t*)x->ix.coll_flag != 0;
+        x->coll_pending = false;
+        if (over) {
+            DeviceIndex full = x->ix;
+            full.coll = nullptr;  // the sort build
+            CallProf cp;
+            if (hipError_t e = launch_index_build(x->d_weak, x->d_strong, full, s, cp.get(), !x->extras_deferred))
+                return e;
+            return hipEventRecord(x->ready, s);
+        }
+    }
     return x->ready ? hipStreamWaitEvent(s, x->ready, 0) : hipSuccess;
 }
+// Order `s` after the index build (a no-op for an index built synchronously): the one place
+// where a stream gets to read the tables of an index built beside its caller.
+hipError_t index_wait(sydelta_index* x, hipStream_t s) {
+    if (!x->ready) return hipSuccess;
+    std::lock_guard<std::mutex> lk(x->build_mu);
+    return index_wait_locked(x, s);
+}
 // A deferred index's filters and tables, built on `s` (after its copies) for a match that needs
-// them; later users order themselves after the build through `ready`.
+// them; later users order themselves after the build through `ready` -- also a second matcher
+// that finds the index built by the first: its own earlier wait was for the copies alone.
 int index_full(sydelta_index* x, hipStream_t s) {
     std::lock_guard<std::mutex> lk(x->build_mu);
+    HIP_TRY(index_wait_locked(x, s));
     if (!x->deferred) return SYDELTA_OK;
-    HIP_TRY(index_wait(x, s));
     CallProf cp;
     HIP_TRY(launch_index_build(x->d_weak, x->d_strong, x->ix, s, cp.get()));
     if (x->ready) HIP_TRY(hipEventRecord(x->ready, s));
@@ -846,6 +878,9 @@ static void index_release(sydelta_index* x) {
     if (x->ready) (void)hipEventSynchronize(x->ready);
     give_mapped(x->stage, kStage);
     x->stage = PinnedHits();
+    x->coll_pending = false;  // (nobody is going to read the tables: no flag to look at)
+    give_mapped(x->coll_pin);
+    x->coll_pin = PinnedHits();
     if (x->d_pool) {
         KeptPool old;
         const hipStream_t home = thread_stream(x->device);
@@ -1141,8 +1176,12 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
     ix.nslots = sl;
     const size_t nb = std::max<uint64_t>(nblocks, 1);
     const size_t sz_weak = up256(4 * nb), sz_strong = up256(8 * nb), sz_filt = up256(4 * fw), sz_t = up256(4 * sl);
-    const size_t sz_order = up256(4 * nb), sz_slot = up256(4 * nb), sz_files = up256(sizeof(FileIx) * nfiles);
-    const size_t sz_fblk = up256(8 * (nfiles + 1)), sz_cstrong = up256(8 * nb);
+    // one file from device arrays: the collision build (DeviceIndex::coll), whose runs lie in
+    // coll_cap entries behind order's and cstrong's first nblocks
+    const size_t ncoll = arrays_on_device && nfiles == 1 && nblocks && nblocks < (1ull << 31) ? index_coll_cap(nblocks) : 0;
+    const size_t sz_coll = ncoll ? 2 * up256(8 * ncoll) + up256(4 * ncoll) + 256 : 0;
+    const size_t sz_order = up256(4 * (nb + ncoll)), sz_slot = up256(4 * nb), sz_files = up256(sizeof(FileIx) * nfiles);
+    const size_t sz_fblk = up256(8 * (nfiles + 1)), sz_cstrong = up256(8 * (nb + ncoll));
     // the level-1 filter of the register-fed scans (k_scan_r at bs 4096, k_scan_g at any
     // other): one file with more keys than an LDS-resident Bloom filter takes
     const bool want_narrow = nfiles == 1 && nblocks > kLdsFilterKeys;
@@ -1163,7 +1202,7 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
                                    : 0;
     const size_t sz_fat = want_l1 ? up256(16 * (size_t)sl) : 0;
     const size_t total = sz_weak + sz_strong + sz_filt + sz_l1 + sz_fat + 4 * sz_t + sz_order + sz_slot + sz_files +
-                         sz_fblk + sz_cstrong + sz_rib;
+                         sz_fblk + sz_cstrong + sz_rib + sz_coll;
     x->d_pool = take_kept_pool(device, total, s, &x->pool_bytes);
     if (!x->d_pool) {
         HIP_TRY(dev_malloc_async(&x->d_pool, total, s));  // stream-ordered: no device-wide synchronization
@@ -1195,6 +1234,16 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
     ix.d_files = (FileIx*)p; p += sz_files;
     ix.d_fblk = (uint64_t*)p; p += sz_fblk;
     ix.cstrong = (uint64_t*)p; p += sz_cstrong;
+    if (ncoll) {
+        ix.coll = (uint2*)p; p += up256(8 * ncoll);
+        ix.coll_runs = (uint2*)p; p += up256(8 * ncoll);
+        ix.coll_link = (uint32_t*)p; p += up256(4 * ncoll);
+        ix.coll_state = (uint32_t*)p; p += 256;
+        ix.coll_cap = (uint32_t)ncoll;
+        if (int r = take_mapped(256, x->coll_pin)) return r;
+        ix.coll_flag = (uint32_t*)x->coll_pin.p;
+        *(volatile uint32_t*)ix.coll_flag = 0;
+    }
     const hipMemcpyKind kind = arrays_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (nblocks) {
         HIP_TRY(hipMemcpyAsync(x->d_weak, weak, 4 * nblocks, kind, s));
@@ -1208,14 +1257,17 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
         if (int r = take_mapped(tb, x->stage, kStage)) return r;
         memcpy(x->stage.p, ix.files.data(), fb);
         memcpy(x->stage.p + ((fb + 15) & ~(size_t)15), x->fblk.data(), 8 * (nfiles + 1));
-        HIP_TRY(hipMemcpyAsync(ix.d_files, x->stage.p, fb, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ix.d_fblk, x->stage.p + ((fb + 15) & ~(size_t)15), 8 * (nfiles + 1),
-                               hipMemcpyHostToDevice, s));
         // one file: on the aux stream, beside the caller's next work; a batch: in the caller's
         // stream order, no host wait (its match follows at once on that stream)
         const hipStream_t sb = nfiles == 1 ? thread_aux_stream(device) : s;
         if (!sb) return fail(SYDELTA_E_OOM, "no stream for the index build");
-        HIP_TRY(stream_after(sb, s, device));
+        // the collision build takes its file table as a kernel argument: it starts after the
+        // signature's copies, and the tables' upload is joined before `ready`
+        if (ix.coll) HIP_TRY(stream_after(sb, s, device));
+        HIP_TRY(hipMemcpyAsync(ix.d_files, x->stage.p, fb, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ix.d_fblk, x->stage.p + ((fb + 15) & ~(size_t)15), 8 * (nfiles + 1),
+                               hipMemcpyHostToDevice, s));
+        if (!ix.coll) HIP_TRY(stream_after(sb, s, device));
         x->ready = take_event(device);
         if (!x->ready) return fail(SYDELTA_E_OOM, "no event for the index build");
         // a batch of small files whose walks self-index (file_walk_ok's index conditions): the
@@ -1226,6 +1278,10 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
         if (!x->deferred) {
             CallProf cp;
             HIP_TRY(launch_index_build(x->d_weak, x->d_strong, ix, sb, cp.get(), !x->extras_deferred));
+        }
+        if (ix.coll) {
+            HIP_TRY(stream_after(sb, s, device));  // the file tables' upload
+            x->coll_pending = true;                // nothing reads the tables before index_wait has settled it
         }
         HIP_TRY(hipEventRecord(x->ready, sb));
         // the ribbon level-1 of a whole-file scan as large as the basis (scan_index), from the
@@ -3199,46 +3255,73 @@ bool chunk_walk_ok(const sydelta_index* idx);  // (below)
 // classifier's own probe rule), or -- a shifted source, where insertions put every later window
 // off the block grid (C3b) -- when 1/4 or more of 256 consecutive blocks mid-file find a hit
 // among their window starts (the walk's roll, k_preroll, on each missed block).  The index
-// must be built (the caller waited for it).
-int copy_heavy(sydelta_index* ix, const uint8_t* d_src, uint64_t len, hipStream_t s, Profiler* prof, bool* heavy) {
-    *heavy = false;
-    const uint64_t n = ix->bs, npos = len - n + 1, nblk = (npos + n - 1) / n;
-    const uint32_t S = 16;
-    const uint64_t np1 = (nblk + S - 1) / S, np2 = std::min<uint64_t>(256, nblk), r0 = (nblk - np2) / 2;
+// must be built before finish (the caller waits for it between the two); begin queues what
+// reads the source alone -- both samples' hashing -- so that it runs beside the index build.
+struct CopyHeavy {
+    sydelta_index* ix;
+    const uint8_t* d_src;
+    uint64_t len;
+    hipStream_t s;
+    Profiler* prof;
     ScratchHold hold;
+    uint64_t n = 0, npos = 0, np1 = 0, np2 = 0, r0 = 0;
+    uint8_t* D = nullptr;
+    uint32_t *h1 = nullptr, *h2 = nullptr;
+    bool fast = false;
+    size_t o_jobs = 0, o_out1 = 0, o_pw1 = 0, o_pst1 = 0, o_out2 = 0, o_pw2 = 0, o_pst2 = 0, o_list = 0, o_cnt = 0;
+    static constexpr uint32_t S = 16;
+    int begin();
+    int finish(bool* heavy);
+};
+int CopyHeavy::begin() {
+    n = ix->bs;
+    npos = len - n + 1;
+    const uint64_t nblk = (npos + n - 1) / n;
+    np1 = (nblk + S - 1) / S;
+    np2 = std::min<uint64_t>(256, nblk);
+    r0 = (nblk - np2) / 2;
     int cur = 0;
     HIP_TRY(hipGetDevice(&cur));
     DevScratch& sc = thread_probe_scratch(cur);
-    const size_t o_jobs = 0, o_out1 = 256, o_pw1 = o_out1 + up256(4 * np1), o_pst1 = o_pw1 + up256(4 * np1);
-    const size_t o_out2 = o_pst1 + up256(8 * np1), o_pw2 = o_out2 + up256(4 * np2), o_pst2 = o_pw2 + up256(4 * np2);
-    const size_t o_list = o_pst2 + up256(8 * np2), o_cnt = o_list + up256(4 * np2), need = o_cnt + 256;
+    o_jobs = 0, o_out1 = 256, o_pw1 = o_out1 + up256(4 * np1), o_pst1 = o_pw1 + up256(4 * np1);
+    o_out2 = o_pst1 + up256(8 * np1), o_pw2 = o_out2 + up256(4 * np2), o_pst2 = o_pw2 + up256(4 * np2);
+    o_list = o_pst2 + up256(8 * np2), o_cnt = o_list + up256(4 * np2);
+    const size_t need = o_cnt + 256;
     if (sc.bytes < need) {
         if (sc.p) (void)hipFreeAsync(sc.p, s);
         sc = DevScratch();
         HIP_TRY(dev_malloc_async(&sc.p, need + need / 4, s));
         sc.bytes = need + need / 4;
     }
-    uint8_t* D = (uint8_t*)sc.p;
+    D = (uint8_t*)sc.p;
     // both samples' results come back after one synchronization: h1 | h2 | the jobs' staging
     PinnedHits& pin = thread_probe_pin();
     if (int r = pinned_at_least(pin, up256(4 * np1) + up256(4 * np2) + 256)) return r;
-    uint32_t* h1 = (uint32_t*)pin.p;
-    uint32_t* h2 = (uint32_t*)(pin.p + up256(4 * np1));
+    h1 = (uint32_t*)pin.p;
+    h2 = (uint32_t*)(pin.p + up256(4 * np1));
     ProbeJob* jobs = (ProbeJob*)(pin.p + up256(4 * np1) + up256(4 * np2));
     jobs[0] = ProbeJob{0, 0, 0, 0, 0};
     jobs[1] = ProbeJob{0, r0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(D + o_jobs, jobs, 2 * sizeof(ProbeJob), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(D + o_cnt, 0, 8, s));
-    const bool fast = ((uintptr_t)d_src & 15) == 0;
+    fast = ((uintptr_t)d_src & 15) == 0;
+    // the windows' hashes (phase 1 reads no table); the shifted sample: 256 consecutive aligned
+    // windows, each miss rolled for its first hit (queued with the first: one round trip for both)
     HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs), 1, np1, S, (uint32_t)n, fast, ix->ix,
-                         (uint32_t*)(D + o_pw1), (uint64_t*)(D + o_pst1), (uint32_t*)(D + o_out1), s, prof));
+                         (uint32_t*)(D + o_pw1), (uint64_t*)(D + o_pst1), (uint32_t*)(D + o_out1), s, prof, 1));
+    HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs) + 1, 1, np2, 1, (uint32_t)n, fast, ix->ix,
+                         (uint32_t*)(D + o_pw2), (uint64_t*)(D + o_pst2), (uint32_t*)(D + o_out2), s, prof, 1));
+    return SYDELTA_OK;
+}
+int CopyHeavy::finish(bool* heavy) {
+    *heavy = false;
+    HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs), 1, np1, S, (uint32_t)n, fast, ix->ix,
+                         (uint32_t*)(D + o_pw1), (uint64_t*)(D + o_pst1), (uint32_t*)(D + o_out1), s, prof, 2));
     HIP_TRY(hipMemcpyAsync(h1, D + o_out1, 4 * np1, hipMemcpyDeviceToHost, s));
-    // the shifted sample: 256 consecutive aligned windows, each miss rolled for its first hit
-    // (queued with the first: one round trip for both)
     uint32_t* d_out2 = (uint32_t*)(D + o_out2);
     uint32_t* d_pw2 = (uint32_t*)(D + o_pw2);
     HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs) + 1, 1, np2, 1, (uint32_t)n, fast, ix->ix, d_pw2,
-                         (uint64_t*)(D + o_pst2), d_out2, s, prof));
+                         (uint64_t*)(D + o_pst2), d_out2, s, prof, 2));
     const DeviceIndex& di = ix->ix;
     WalkArgs a{};
     a.base = d_src;
@@ -3303,6 +3386,16 @@ extern "C" int sydelta_match_device(sydelta_index* idx, const uint8_t* d_src, ui
             idx->rib_stream = s;
         }
     }
+    // a copy-heavy source is walked by K10 as one chunk (generator.rs:116-221 on the device);
+    // a literal-heavy one by the classifier, whose probe sample would say the same (mode 0).
+    // The sample's hashing is queued first: it reads the source alone and runs beside the
+    // index build, which the host then waits for (index_wait reads the build's overflow flag).
+    const bool sample = chunk_walk_ok(idx) && probe_mode_env() < 0 && len >= idx->bs && idx->fblk[1] > 0 &&
+                        ((uintptr_t)d_src & 15) == 0;
+    CallProf cp_sample;
+    CopyHeavy sampler{idx, d_src, len, s, cp_sample.get()};
+    if (sample)
+        if (int r = sampler.begin()) return r;
     // the scan's extras (level-1 Bloom, fat table: scan_index) on the ribbon's stream, beside
     // the copy-heavy sample below, so that a literal-heavy source's scan finds them built (a
     // copy-heavy one has spent ~0.06 ms of a few CUs)
@@ -3311,7 +3404,7 @@ extern "C" int sydelta_match_device(sydelta_index* idx, const uint8_t* d_src, ui
         if (idx->extras_deferred && !idx->deferred) {
             const hipStream_t sx = thread_walk_stream(idx->device, 2);
             if (sx) {
-                HIP_TRY(index_wait(idx, sx));
+                HIP_TRY(index_wait_locked(idx, sx));
                 CallProf cp;
                 HIP_TRY(launch_index_extras(idx->d_weak, idx->ix, sx, cp.get()));
                 if (!idx->extras_ev && !(idx->extras_ev = take_event(idx->device)))
@@ -3322,16 +3415,11 @@ extern "C" int sydelta_match_device(sydelta_index* idx, const uint8_t* d_src, ui
             }
         }
     }
-    // a copy-heavy source is walked by K10 as one chunk (generator.rs:116-221 on the device);
-    // a literal-heavy one by the classifier, whose probe sample would say the same (mode 0)
-    if (chunk_walk_ok(idx) && probe_mode_env() < 0 && len >= idx->bs && idx->fblk[1] > 0 &&
-        ((uintptr_t)d_src & 15) == 0) {
+    if (sample) {
         HIP_TRY(index_wait(idx, s));
         bool heavy = false;
-        {
-            CallProf cp;
-            if (int r = copy_heavy(idx, d_src, len, s, cp.get(), &heavy)) return r;
-        }
+        if (int r = sampler.finish(&heavy)) return r;
+        cp_sample.prof.resolve();
         if (heavy) {
             sydelta_chunk* ch = nullptr;
             if (int r = sydelta_chunk_classify(idx, d_src, 0, len, len, 0, len, s, &ch)) return r;

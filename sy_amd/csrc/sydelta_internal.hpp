@@ -120,9 +120,24 @@ struct DeviceIndex {
     uint32_t* cnt = nullptr;    // candidates per slot
     uint32_t* start = nullptr;  // exclusive prefix of cnt (global positions into order)
     uint32_t* fill = nullptr;   // scratch for the scatter
-    uint32_t* order = nullptr;  // global block indices grouped by slot (any order within a slot)
+    uint32_t* order = nullptr;  // a slot's candidates, ascending: order[start[sl] .. start[sl] + cnt[sl])
     uint64_t* cstrong = nullptr;  // strong hash of order[j]
     uint32_t* slot_of = nullptr;
+    // The collision build of a single-file index (launch_index_build with coll set): block i is
+    // entry i of order / cstrong, and only the weak values that several blocks share get a run,
+    // in the coll_cap entries behind the first nblocks (k_idx_fix_*).  coll lists the blocks
+    // that found their weak value in the table (slot, block); coll_link chains a slot's listed
+    // blocks (fill[slot]: the last one); coll_runs holds, at a chain's head, the run's position
+    // and the slot's owner; coll_state = {list length, overflow, entries of the region taken};
+    // *coll_flag (mapped host memory, zero before the build) is set when list and owners exceed
+    // coll_cap or a run is too long to chain: the tables are then unusable and the sort build
+    // has to run (coll = nullptr).
+    uint2* coll = nullptr;
+    uint32_t* coll_link = nullptr;
+    uint2* coll_runs = nullptr;
+    uint32_t* coll_state = nullptr;
+    uint32_t* coll_flag = nullptr;
+    uint32_t coll_cap = 0;
     FileIx* d_files = nullptr;  // per-file offsets (device copy of files)
     uint64_t* d_fblk = nullptr; // block prefix over files, nfiles+1 entries
     std::vector<FileIx> files;  // host copy
@@ -156,6 +171,15 @@ hipError_t launch_signature_batch(const uint8_t* d_buf, const uint64_t* d_off, c
 // extras = false leaves the scans' level-1 filter and fat table (ix.l1, ix.fat) unfilled:
 // launch_index_extras fills them when a scan first needs them (the chunk walk and the aligned
 // probe read only the Bloom filter and the exact table).
+// With ix.coll set (one file, no fat table wanted now) the candidates are not sorted: the
+// collision build (DeviceIndex::coll) orders only the blocks whose weak value another block
+// shares, and *ix.coll_flag tells, once the build has run, whether it has to be repeated with
+// coll = nullptr.  Nothing may read start / cnt / order / cstrong before the flag has been read.
+constexpr uint32_t index_coll_cap(uint64_t nblocks) {  // entries of the collision region (a power of two)
+    uint32_t c = 4096;
+    while (c < nblocks / 64) c <<= 1;
+    return c;
+}
 hipError_t launch_index_build(const uint32_t* d_weak, const uint64_t* d_strong, DeviceIndex& ix, hipStream_t s,
                               Profiler* prof, bool extras = true);
 hipError_t launch_index_extras(const uint32_t* d_weak, const DeviceIndex& ix, hipStream_t s, Profiler* prof);

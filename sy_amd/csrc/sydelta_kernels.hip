@@ -238,6 +238,154 @@ __global__ void k_idx_insert(const uint32_t* __restrict__ weak, uint64_t n, cons
     }
 }
 
+// ---------------------------------------------------------------------------
+// The collision build of a single-file index (DeviceIndex::coll)
+// ---------------------------------------------------------------------------
+// Nearly every weak value of a signature belongs to one block (1 Mi random blocks: ~500 share
+// theirs), so instead of sorting all (slot, block) pairs to group a slot's candidates, block i
+// is entry i of order / cstrong and a slot's owner (the block whose CAS took it) points the
+// slot at itself (start = i; cnt is 1 from the clear).  The few blocks that find their weak
+// value in the table are listed (coll) and chained per slot (fill[slot]: the last listed,
+// coll_link: the one listed before), each counted in cnt[slot].  k_idx_fix_runs then takes
+// every such slot's run from the coll_cap entries behind the first n, and k_idx_fix_place
+// puts the owner and the listed blocks there, ascending.  A list that does not fit the region
+// together with the owners, or a run above kFixMaxRun blocks (each of its blocks walks the
+// chain), sets the overflow words and leaves the tables unusable.
+constexpr uint32_t kFixNil = 0xFFFFFFFFu;
+constexpr uint32_t kFixMaxRun = 256;
+
+// The tables' clears in one launch (16-byte units): filt and l1 zero, keys kEmptyKey, cnt 1,
+// fill kFixNil, state zero.
+__global__ __launch_bounds__(256) void k_idx_clear(uint4* __restrict__ filt, uint64_t nfilt, uint4* __restrict__ l1,
+                                                   uint64_t nl1, uint4* __restrict__ keys, uint4* __restrict__ cnt,
+                                                   uint4* __restrict__ fill, uint64_t nslots4,
+                                                   uint32_t* __restrict__ state) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    if (i0 < 4) state[i0] = 0;
+    const uint4 z = make_uint4(0, 0, 0, 0), e = make_uint4(kEmptyKey, kEmptyKey, kEmptyKey, kEmptyKey);
+    const uint4 one = make_uint4(1, 1, 1, 1);
+    for (uint64_t i = i0; i < nfilt; i += step) filt[i] = z;
+    for (uint64_t i = i0; i < nl1; i += step) l1[i] = z;
+    for (uint64_t i = i0; i < nslots4; i += step) {
+        keys[i] = e;
+        cnt[i] = one;
+        fill[i] = e;  // kFixNil
+    }
+}
+
+// k_idx_insert for one file: the file's table by value, order / cstrong written in passing.
+__global__ void k_idx_insert_one(const uint32_t* __restrict__ weak, const uint64_t* __restrict__ strong, uint32_t n,
+                                 FileIx F, uint32_t* __restrict__ filt, uint32_t* __restrict__ l1, uint32_t l1_wshift,
+                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ start, uint32_t* __restrict__ cnt,
+                                 uint32_t* __restrict__ fill, uint32_t* __restrict__ order,
+                                 uint64_t* __restrict__ cstrong, uint2* __restrict__ coll, uint32_t* __restrict__ link,
+                                 uint32_t cap, uint32_t* __restrict__ state) {
+    const uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i64 >= n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t w = weak[i];
+    order[i] = i;
+    cstrong[i] = strong[i];
+    const ProbeHash h = probe_hash(w);
+    atomicOr(filt + F.filt_off + (h.r >> F.fwshift), filt_mask(h.q));
+    if (l1)
+        atomicOr(l1 + (l1_wshift == 1 ? (size_t)l1r_word(h.q) : (size_t)(h.q >> l1_wshift)), 1u << (h.q & 31));
+    uint32_t b = bucket_hash(w) & F.bmask;
+    for (;;) {
+        const uint64_t s0 = F.slot_off + 4ull * b;
+        const uint4 v = *(const uint4*)(keys + s0);
+        const uint32_t cur[4] = {v.x, v.y, v.z, v.w};
+        for (uint32_t j = 0; j < 4; ++j) {
+            uint32_t old = cur[j];
+            if (old == kEmptyKey) {
+                old = atomicCAS(&keys[s0 + j], kEmptyKey, w);
+                if (old == kEmptyKey) {  // the slot's owner
+                    start[s0 + j] = i;
+                    return;
+                }
+            }
+            if (old == w) {  // another block owns the slot: listed (counted even where the list is full)
+                const uint32_t at = atomicAdd(&state[0], 1u);
+                if (at < cap) {
+                    coll[at] = make_uint2((uint32_t)(s0 + j), i);
+                    link[at] = atomicExch(&fill[s0 + j], at);
+                    atomicAdd(&cnt[s0 + j], 1u);
+                }
+                return;
+            }
+        }
+        b = (b + 1) & F.bmask;
+    }
+}
+
+__device__ __forceinline__ void fix_overflow(uint32_t* state, uint32_t* host_flag) {
+    __hip_atomic_store(&state[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(host_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One thread per listed block: the first listed of its slot (nothing linked before it) takes the
+// run's entries -- cnt[slot], the owner included -- from the region (state[2]) and leaves the
+// run's position and the owner with the chain's head (runs[fill[slot]]), where every block of
+// the slot finds them.  n: the index's blocks (the region starts at entry n).
+__global__ __launch_bounds__(256) void k_idx_fix_runs(const uint2* __restrict__ coll, const uint32_t* __restrict__ link,
+                                                      uint32_t cap, uint32_t* __restrict__ state,
+                                                      uint32_t* __restrict__ host_flag,
+                                                      const uint32_t* __restrict__ start,
+                                                      const uint32_t* __restrict__ cnt,
+                                                      const uint32_t* __restrict__ fill, uint2* __restrict__ runs,
+                                                      uint32_t n) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t L = state[0];
+    if (L > cap) {  // the list itself did not fit
+        if (e == 0) fix_overflow(state, host_flag);
+        return;
+    }
+    if (e >= L || link[e] != kFixNil) return;
+    const uint32_t sl = coll[e].x, total = cnt[sl];
+    if (total > kFixMaxRun) {
+        fix_overflow(state, host_flag);
+        return;
+    }
+    const uint32_t base = atomicAdd(&state[2], total);
+    if (base + total > cap) {  // list and owners exceed the region: the sum says so in any order
+        fix_overflow(state, host_flag);
+        return;
+    }
+    runs[fill[sl]] = make_uint2(n + base, start[sl]);
+}
+
+// Each listed block into its run, at the number of the run's blocks below it (the chain walked
+// once); the slot's first listed block places the owner too and points the slot at the run.
+// Nothing on overflow.
+__global__ __launch_bounds__(256) void k_idx_fix_place(const uint2* __restrict__ coll, const uint32_t* __restrict__ link,
+                                                       uint32_t cap, const uint32_t* __restrict__ state,
+                                                       const uint32_t* __restrict__ fill,
+                                                       const uint2* __restrict__ runs,
+                                                       const uint64_t* __restrict__ strong,
+                                                       uint32_t* __restrict__ start, uint32_t* __restrict__ order,
+                                                       uint64_t* __restrict__ cstrong) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (state[1] || state[0] > cap || e >= state[0]) return;
+    const uint2 me = coll[e];
+    const bool first = link[e] == kFixNil;
+    const uint2 run = runs[fill[me.x]];  // {position, owner}
+    uint32_t below = run.y < me.y ? 1u : 0u, obelow = 0;
+    uint32_t at = fill[me.x];
+    for (uint32_t k = 0; k < kFixMaxRun && at != kFixNil; ++k) {
+        const uint32_t blk = coll[at].y;
+        below += blk < me.y;
+        obelow += blk < run.y;
+        at = link[at];
+    }
+    order[run.x + below] = me.y;
+    cstrong[run.x + below] = strong[me.y];
+    if (first) {
+        order[run.x + obelow] = run.y;
+        cstrong[run.x + obelow] = strong[run.y];
+        start[me.x] = run.x;
+    }
+}
+
 // Insert equation (start column s, coefficients c with bit 0 set) into a shard's echelon
 // rows (rows[j]: the row whose pivot is column j, bit k = column j + k; 0 = none).  Rows
 // are written once (CAS from 0) and never change, so the lanes of a wave insert their keys
@@ -4573,6 +4721,30 @@ hipError_t launch_index_extras(const uint32_t* d_weak, const DeviceIndex& ix, hi
 hipError_t launch_index_build(const uint32_t* d_weak, const uint64_t* d_strong, DeviceIndex& ix, hipStream_t s,
                               Profiler* prof, bool extras) {
     hipError_t e;
+    if (ix.coll && ix.nfiles == 1 && !(extras && ix.fat)) {  // the collision build (DeviceIndex::coll)
+        const bool l1 = extras && ix.l1;
+        const uint64_t nl1 = l1 ? l1_total_words(ix.l1_wshift) / 4 : 0, n16 = std::max(ix.fwords / 4 + nl1, ix.nslots / 4);
+        hipLaunchKernelGGL(k_idx_clear, dim3((uint32_t)std::min<uint64_t>(grid_for(n16, 256), 4096)), dim3(256), 0,
+                           s, (uint4*)ix.filt, ix.fwords / 4, (uint4*)ix.l1, nl1, (uint4*)ix.keys, (uint4*)ix.cnt,
+                           (uint4*)ix.fill, ix.nslots / 4, ix.coll_state);
+        if ((e = hipGetLastError())) return e;
+        const uint32_t n = (uint32_t)ix.nblocks, cap = ix.coll_cap;
+        if (n == 0) return hipSuccess;
+        {
+            ProfScope ps(prof, s, "k_idx_insert");
+            hipLaunchKernelGGL(k_idx_insert_one, dim3(grid_for(n, 256)), dim3(256), 0, s, d_weak, d_strong, n,
+                               ix.files[0], ix.filt, l1 ? ix.l1 : nullptr, ix.l1_wshift, ix.keys, ix.start, ix.cnt,
+                               ix.fill, ix.order, ix.cstrong, ix.coll, ix.coll_link, cap, ix.coll_state);
+        }
+        if ((e = hipGetLastError())) return e;
+        ProfScope ps(prof, s, "k_idx_fix");
+        hipLaunchKernelGGL(k_idx_fix_runs, dim3(cap / 256), dim3(256), 0, s, ix.coll, ix.coll_link, cap,
+                           ix.coll_state, ix.coll_flag, ix.start, ix.cnt, ix.fill, ix.coll_runs, n);
+        if ((e = hipGetLastError())) return e;
+        hipLaunchKernelGGL(k_idx_fix_place, dim3(cap / 256), dim3(256), 0, s, ix.coll, ix.coll_link, cap,
+                           ix.coll_state, ix.fill, ix.coll_runs, d_strong, ix.start, ix.order, ix.cstrong);
+        return hipGetLastError();
+    }
     if ((e = hipMemsetAsync(ix.filt, 0, ix.fwords * 4, s))) return e;
     if (extras && ix.l1 && (e = hipMemsetAsync(ix.l1, 0, l1_total_words(ix.l1_wshift) * 4, s))) return e;
     if ((e = hipMemsetAsync(ix.keys, 0xFF, ix.nslots * 4, s))) return e;
