@@ -36,6 +36,7 @@ import numpy as np
 import pytest
 
 import zstd_frames as F
+from test_unzstd_host import FORMS_OK, FORMS_REJECT
 from test_zstd import _libzstd, ref_compress
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,6 +87,13 @@ def corpus_dir(tmp_path_factory):
         put(name, "ok", frame, data)
     for name, frame in F.malformed().items():
         put(name, "reject", frame)
+    # the assembled families test_unzstd_host.py mutates, and the ones it has refused: each
+    # refused one, a twin one byte short of its offset among them, between good frames
+    for name in FORMS_OK:
+        frame, ops = F.form(name)
+        put(name, "ok", frame, F.expect(ops).tobytes())
+    for name in FORMS_REJECT:
+        put(name, "reject", F.form_refused(name))
     (d / "manifest.txt").write_text("\n".join(lines) + "\n")
     return str(d)
 
@@ -99,9 +107,12 @@ def test_batch_stages_under_asan_ubsan(corpus_dir):
     assert "unzstd_batch_check ok" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
     rejects = {ln.split()[1].rstrip(":"): ln for ln in r.stdout.splitlines() if ln.startswith("reject ")}
+    forms = {name: rejects.pop(name) for name in FORMS_REJECT}
     assert sorted(rejects) == sorted(F.malformed()) == sorted(F.MALFORMED_REASON)
     for name, line in rejects.items():  # each refused for its own reason, its file named
         assert "file 1: zstd frame: block " in line and F.MALFORMED_REASON[name] in line, line
+    for name, line in forms.items():
+        assert "file 1: zstd frame: " + F.FORMS_REFUSED[name] in line, line
     limit = [ln for ln in r.stdout.splitlines() if ln.startswith("limit: ")]
     assert len(limit) == 1 and "the batch regenerates" in limit[0] and "split it below 4 GiB" in limit[0]
     refused = [ln[len("refuse "):] for ln in r.stdout.splitlines() if ln.startswith("refuse ")]

@@ -10,7 +10,12 @@ exact sizes and all alignments) over
   direct-representation weights and 14-byte headers;
 * hand-assembled frames (RLE literals, RLE_Mode sequences, all three sequence-count forms),
   each checked against libzstd first;
-* the fixed malformed list: an error each, nothing written;
+* the families assembled from RFC 8878 for the forms no sender writes (tests/zstd_frames.py:
+  offset codes 17 to 21 and 24, the length extremes, 12-bit Huffman trees, deep chains, empty
+  and many blocks), every frame of every family checked against libzstd first, and a libzstd
+  frame with a match 5 MiB back; the larger ones decoded only, not mutated;
+* the fixed malformed list, the twins one byte short of their offset and the block of 128 KiB + 1:
+  an error each that names its block, nothing written;
 * 200 seeded mutants of every one of these frames: never a sanitizer report; whenever libzstd
   accepts a mutant, the same bytes, or a refusal whose condition the program finds in the
   frame's bytes with a reader of its own (the issue's own refusals and RFC 8878's limits that
@@ -35,6 +40,13 @@ OUT = os.path.join(ROOT, "build", "asan")
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None or _libzstd() is None or
                                 not os.path.exists("/opt/rocm/include/hip/hip_runtime.h"),
                                 reason="needs g++, the HIP headers and the system libzstd")
+
+
+# The assembled families of tests/zstd_frames.py: mutated 200 times, decoded at exact sizes only
+# (the large ones; wide-seq's 32 MiB take the program ten seconds), and refused.
+FORMS_OK = ("of17", "ml-max", "ll-max") + F.HUF_FORMS + ("deep1-1", "deep1-2", "deep3", "empties", "empties-seq")
+FORMS_VALID = ("of18", "of19", "of20", "of21", "wide-seq", "deep1-3", "deep1-64", "deep-block", "many-blocks")
+FORMS_REJECT = tuple(f"of{k}-short" for k in range(17, 22)) + ("ml-over",)
 
 
 def _build(name: str, extra=()) -> str:
@@ -72,6 +84,12 @@ def corpus_dir(tmp_path_factory):
         put(name, "ok", frame, data)
     for name, frame in F.malformed().items():
         put(name, "reject", frame)
+    for name in FORMS_OK + FORMS_VALID:
+        frame, ops = F.form(name)
+        put(name, "ok" if name in FORMS_OK else "valid", frame, F.expect(ops).tobytes())
+    put("far-s19", "valid", *F.far_frame())
+    for name in FORMS_REJECT:
+        put(name, "reject", F.form_refused(name))
     (d / "manifest.txt").write_text("\n".join(lines) + "\n")
     return str(d)
 
@@ -119,19 +137,60 @@ def _assert_hand_assembled_frames_are_what_libzstd_reads():
     assert F.libzstd_accepts(bad["first-block-repeat-mode"], 1 << 20) is None
 
 
+def _assert_table_descriptions_reach_what_they_claim():
+    """The FSE table descriptions read from the spec (F.read_ncount): what the corpus reaches, and
+    what the far frame adds to it."""
+    logs, less, top = [0, 0, 0], [False] * 3, [0, 0, 0]
+    for name, (frame, _) in F.corpus().items():
+        for tabs in F.fse_tables(frame):
+            for j, (log, probs) in tabs.items():
+                logs[j], less[j], top[j] = max(logs[j], log), less[j] or -1 in probs, max(top[j], len(probs) - 1)
+    assert logs == [9, 8, 9] and all(less), (logs, less)  # LL / OF / ML at their largest accuracy logs
+    assert top[0] < 32 and top[1] < 22, top  # which is why the far frame is there
+    frame, data = F.far_frame()
+    assert zstd_decode(frame, len(data)) == data
+    tabs = F.fse_tables(frame)
+    assert any(len(t[1][1]) - 1 >= 22 for t in tabs if 1 in t)  # an FSE-compressed offset table with code 22
+    assert any(len(t[0][1]) - 1 >= 32 for t in tabs if 0 in t)  # and a literal-length table with code 32
+
+
+def _assert_assembled_families_are_what_libzstd_reads():
+    """Every frame of every family, the GPU test's large ones included."""
+    import numpy as np
+
+    for name in F.FORMS:
+        frame, ops = F.form(name)
+        want = F.expect(ops)
+        got = zstd_decode(frame, len(want) + 1)
+        assert len(got) == len(want) and np.array_equal(np.frombuffer(got, dtype=np.uint8), want), name
+    assert len(F.expect(F.form("of27")[1])) == (1 << 28) + 44
+    for name in ("ml-max", "ll-max"):
+        assert len(F.expect(F.form(name)[1])) == 128 << 10
+    assert max(b["lit_regen"] for b in F.describe(F.form("huf12-4x131072")[0])["blocks"]) == 131072
+    for name in F.FORMS_REFUSED:
+        got = F.libzstd_accepts(F.form_refused(name), 1 << 29)
+        # libzstd 1.4.8 accepts the block of 128 KiB + 1: stricter here by design
+        assert (got is not None and len(got) == (128 << 10) + 1) if name == "ml-over" else got is None, name
+
+
 @pytest.mark.timeout(1800)
 def test_stage_bodies_under_asan_ubsan(corpus_dir):
     _assert_corpus_covers_what_it_claims()
     _assert_hand_assembled_frames_are_what_libzstd_reads()
+    _assert_table_descriptions_reach_what_they_claim()
+    _assert_assembled_families_are_what_libzstd_reads()
     r = _run(_build("unzstd_check"), corpus_dir, 200)
     print(r.stdout[-3000:])
     assert r.returncode == 0, (r.stdout[-4000:], r.stderr[-6000:])
     assert "unzstd_check ok" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
     rejects = {ln.split()[1].rstrip(":"): ln for ln in r.stdout.splitlines() if ln.startswith("reject ")}
+    forms = {name: rejects.pop(name) for name in FORMS_REJECT}
     assert sorted(rejects) == sorted(F.malformed()) == sorted(F.MALFORMED_REASON)
     for name, line in rejects.items():  # each refused for its own reason
         assert F.MALFORMED_REASON[name] in line, line
+    for name, line in forms.items():  # and at its own block
+        assert F.FORMS_REFUSED[name] in line, line
 
 
 @pytest.mark.timeout(900)
@@ -139,3 +198,5 @@ def test_planted_bug_is_caught(corpus_dir):
     r = _run(_build("unzstd_check_bug", ["-DUNZSTD_PLANT_BUG"]), corpus_dir, 0)
     assert r.returncode != 0
     assert "AddressSanitizer" in r.stderr or "FAIL ll0-offset-before-start" in r.stdout
+    # the twins one byte short of their offset are accepted by that build as well
+    assert "AddressSanitizer" in r.stderr or any(f"FAIL of{k}-short: accepted" in r.stdout for k in range(17, 22))
