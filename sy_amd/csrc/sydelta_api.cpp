@@ -674,6 +674,7 @@ struct sydelta_index {
     // build and every use waits for it on its own stream (index_wait), so work the caller
     // queues meanwhile -- C5's aligned probe of the source -- overlaps the build.
     hipEvent_t ready = nullptr;
+    hipStream_t build_stream = nullptr;  // ... that stream (a library thread stream: never destroyed)
     PinnedHits stage;  // the file tables' upload (mapped; returned at release)
     uint64_t max_nblk = 0;  // the most blocks of any file
     // A batch whose walks are self-indexed (K10 builds each file's filter and table in LDS from
@@ -691,6 +692,9 @@ struct sydelta_index {
     // only the Bloom filter and the exact table (C5: 1-8 Mi keys).  extras_ev orders scans on
     // other streams after them.
     bool extras_deferred = false;
+    // ... except the level-1 Bloom where they were queued for a scan that takes the ribbon
+    // (DeviceIndex::extras_parts): the first scan that reads the Bloom fills it (scan_index)
+    bool l1_deferred = false;
     hipEvent_t extras_ev = nullptr;
     hipStream_t extras_stream = nullptr;
 };
@@ -711,9 +715,15 @@ hipError_t index_wait_locked(sydelta_index* x, hipStream_t s) {
         if (over) {
             DeviceIndex full = x->ix;
             full.coll = nullptr;  // the sort build
+            // extras queued behind the build before its flag was read (sydelta_match_device) left
+            // the fat table alone; the rebuild, which fills level-1 and the fat table again,
+            // follows them
+            if (x->extras_ev && x->extras_stream != s)
+                if (hipError_t e = hipStreamWaitEvent(s, x->extras_ev, 0)) return e;
             CallProf cp;
             if (hipError_t e = launch_index_build(x->d_weak, x->d_strong, full, s, cp.get(), !x->extras_deferred))
                 return e;
+            if (!x->extras_deferred) x->l1_deferred = false;
             return hipEventRecord(x->ready, s);
         }
     }
@@ -1278,6 +1288,7 @@ static int index_create_impl(int device, const uint32_t* weak, const uint64_t* s
         if (!x->deferred) {
             CallProf cp;
             HIP_TRY(launch_index_build(x->d_weak, x->d_strong, ix, sb, cp.get(), !x->extras_deferred));
+            x->build_stream = sb;
         }
         if (ix.coll) {
             HIP_TRY(stream_after(sb, s, device));  // the file tables' upload
@@ -1934,6 +1945,16 @@ static hipError_t scan_index(sydelta_index* x, uint64_t tot_pos, hipStream_t s, 
             x->extras_stream = s;
         } else if (x->extras_ev && x->extras_stream != s) {
             if (hipError_t e = hipStreamWaitEvent(s, x->extras_ev, 0)) return e;
+        }
+        // the Bloom left out for a ribbon scan (l1_deferred), wanted now: filled here, behind
+        // the other extras, and extras_ev moves to this stream (a wait takes the latest record)
+        if (x->l1_deferred && (x->rib_mode == 0 || (x->rib_mode == 1 && tot_pos < kRibMinScan))) {
+            DeviceIndex bl = x->ix;
+            bl.extras_parts = 1;
+            if (hipError_t e = launch_index_extras(x->d_weak, bl, s, prof)) return e;
+            if (hipError_t e = hipEventRecord(x->extras_ev, s)) return e;
+            x->l1_deferred = false;
+            x->extras_stream = s;
         }
     }
     if (x->rib_mode == 0 || (x->rib_mode == 1 && tot_pos < kRibMinScan)) return hipSuccess;
@@ -3255,7 +3276,8 @@ bool chunk_walk_ok(const sydelta_index* idx);  // (below)
 // classifier's own probe rule), or -- a shifted source, where insertions put every later window
 // off the block grid (C3b) -- when 1/4 or more of 256 consecutive blocks mid-file find a hit
 // among their window starts (the walk's roll, k_preroll, on each missed block).  The index
-// must be built before finish (the caller waits for it between the two); begin queues what
+// must be built before finish runs on the device (the caller orders its stream after the build
+// between the two, and with `skip` set need not have read the build's overflow flag); begin queues what
 // reads the source alone -- both samples' hashing -- so that it runs beside the index build.
 struct CopyHeavy {
     sydelta_index* ix;
@@ -3268,10 +3290,16 @@ struct CopyHeavy {
     uint8_t* D = nullptr;
     uint32_t *h1 = nullptr, *h2 = nullptr;
     bool fast = false;
+    // finish queued behind a collision build whose flag nobody has read: DeviceIndex::coll_skip
+    const uint32_t* skip = nullptr;
     size_t o_jobs = 0, o_out1 = 0, o_pw1 = 0, o_pst1 = 0, o_out2 = 0, o_pw2 = 0, o_pst2 = 0, o_list = 0, o_cnt = 0;
     static constexpr uint32_t S = 16;
     int begin();
     int finish(bool* heavy);
+    int again() {  // before a second finish: the pre-roll's miss count
+        HIP_TRY(hipMemsetAsync(D + o_cnt, 0, 8, s));
+        return SYDELTA_OK;
+    }
 };
 int CopyHeavy::begin() {
     n = ix->bs;
@@ -3315,15 +3343,17 @@ int CopyHeavy::begin() {
 }
 int CopyHeavy::finish(bool* heavy) {
     *heavy = false;
-    HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs), 1, np1, S, (uint32_t)n, fast, ix->ix,
+    DeviceIndex di = ix->ix;
+    di.coll_skip = skip;
+    HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs), 1, np1, S, (uint32_t)n, fast, di,
                          (uint32_t*)(D + o_pw1), (uint64_t*)(D + o_pst1), (uint32_t*)(D + o_out1), s, prof, 2));
     HIP_TRY(hipMemcpyAsync(h1, D + o_out1, 4 * np1, hipMemcpyDeviceToHost, s));
     uint32_t* d_out2 = (uint32_t*)(D + o_out2);
     uint32_t* d_pw2 = (uint32_t*)(D + o_pw2);
-    HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs) + 1, 1, np2, 1, (uint32_t)n, fast, ix->ix, d_pw2,
+    HIP_TRY(launch_probe(d_src, (const ProbeJob*)(D + o_jobs) + 1, 1, np2, 1, (uint32_t)n, fast, di, d_pw2,
                          (uint64_t*)(D + o_pst2), d_out2, s, prof, 2));
-    const DeviceIndex& di = ix->ix;
     WalkArgs a{};
+    a.skip = skip;
     a.base = d_src;
     a.n = (uint32_t)n;
     a.nm = (uint32_t)(n % 65521);
@@ -3396,17 +3426,35 @@ extern "C" int sydelta_match_device(sydelta_index* idx, const uint8_t* d_src, ui
     CopyHeavy sampler{idx, d_src, len, s, cp_sample.get()};
     if (sample)
         if (int r = sampler.begin()) return r;
-    // the scan's extras (level-1 Bloom, fat table: scan_index) on the ribbon's stream, beside
-    // the copy-heavy sample below, so that a literal-heavy source's scan finds them built (a
-    // copy-heavy one has spent ~0.06 ms of a few CUs)
+    // the scan's extras (level-1 Bloom, fat table: scan_index) on the stream that built the
+    // index, directly behind the build and beside the ribbon and the copy-heavy sample below,
+    // so that a literal-heavy source's scan finds them built (a copy-heavy one has spent
+    // ~0.06 ms of a few CUs).  Nothing is waited for: behind a collision build that nobody has
+    // looked at, the fat table's fill reads no table if the build overflowed (coll_skip), and
+    // the rebuild fills both (index_wait_locked).  On the ribbon's stream they ran behind the
+    // ribbon, the longest piece of work before the scan, and ended the stretch.
     if (idx->nfiles == 1 && s == idx->stream && npos_all) {
         std::lock_guard<std::mutex> lk(idx->build_mu);
         if (idx->extras_deferred && !idx->deferred) {
-            const hipStream_t sx = thread_walk_stream(idx->device, 2);
+            // (build_stream is set by the build at creation; an index without it -- none today,
+            // extras_deferred implies that build -- would take the ribbon's stream and, below, the
+            // host's wait for the build, as before)
+            const hipStream_t sx = idx->build_stream ? idx->build_stream : thread_walk_stream(idx->device, 2);
             if (sx) {
-                HIP_TRY(index_wait_locked(idx, sx));
+                DeviceIndex ex = idx->ix;
+                if (sx == idx->build_stream && idx->coll_pending && idx->ix.coll_state)
+                    ex.coll_skip = idx->ix.coll_state;
+                else
+                    HIP_TRY(index_wait_locked(idx, sx));
+                // the Bloom's fill (1 Mi atomics, ~45 us beside the sample's lookups) is left to the
+                // first scan that reads it when this call's scan will take the ribbon
+                if (idx->ix.rib_l1 && idx->ix.fat &&
+                    (idx->rib_mode == 2 || (idx->rib_mode == 1 && npos_all >= kRibMinScan))) {
+                    ex.extras_parts = 2;
+                    idx->l1_deferred = true;
+                }
                 CallProf cp;
-                HIP_TRY(launch_index_extras(idx->d_weak, idx->ix, sx, cp.get()));
+                HIP_TRY(launch_index_extras(idx->d_weak, ex, sx, cp.get()));
                 if (!idx->extras_ev && !(idx->extras_ev = take_event(idx->device)))
                     return fail(SYDELTA_E_OOM, "no event");
                 HIP_TRY(hipEventRecord(idx->extras_ev, sx));
@@ -3416,9 +3464,34 @@ extern "C" int sydelta_match_device(sydelta_index* idx, const uint8_t* d_src, ui
         }
     }
     if (sample) {
-        HIP_TRY(index_wait(idx, s));
         bool heavy = false;
+        {
+            std::lock_guard<std::mutex> lk(idx->build_mu);
+            if (idx->coll_pending && idx->ready && idx->ix.coll_state && idx->ix.coll_flag) {
+                // no host wait for the collision build in the middle of the verdict: the lookups
+                // and the pre-roll are queued behind `ready` on the device and read no table if
+                // the build overflowed (coll_skip); the flag is read after the sample's one
+                // synchronization, and an overflow repeats them after the rebuild
+                HIP_TRY(hipStreamWaitEvent(s, idx->ready, 0));
+                sampler.skip = idx->ix.coll_state;
+            } else {
+                HIP_TRY(index_wait_locked(idx, s));
+            }
+        }
+        // build_mu is not held over the sample: another matcher of this index may settle the
+        // build meanwhile (and rebuild it on its stream: the state's overflow word stays set, so
+        // the kernels queued here still leave the tables alone)
         if (int r = sampler.finish(&heavy)) return r;
+        if (sampler.skip) {
+            sampler.skip = nullptr;
+            // (finish has synchronized behind `ready`: the flag is final)
+            const bool over = *(volatile uint32_t*)idx->ix.coll_flag != 0;
+            HIP_TRY(index_wait(idx, s));  // settles coll_pending unless another has; rebuilds on overflow
+            if (over) {
+                if (int r = sampler.again()) return r;
+                if (int r = sampler.finish(&heavy)) return r;
+            }
+        }
         cp_sample.prof.resolve();
         if (heavy) {
             sydelta_chunk* ch = nullptr;

@@ -598,9 +598,10 @@ __global__ __launch_bounds__(64, 4) void k_walk_files(WalkArgs a) {
 // beforehand, one wave per miss: the walk then reads each miss's result instead.
 // The misses are listed first (one thread per block, a wave-aggregated atomic).
 __global__ __launch_bounds__(1024) void k_miss_list(const uint32_t* ahit, uint64_t b0, uint64_t b1, uint32_t* list,
-                                                    unsigned long long* count) {
+                                                    unsigned long long* count, const uint32_t* skip) {
     __shared__ uint32_t wc[64];  // per (wave, quarter): misses, then their list offset
     __shared__ uint32_t wbase;
+    if (skip && skip[1]) return;  // (launch_preroll: the collision build overflowed; ahit was not written)
     const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
     const uint64_t g = b0 + (uint64_t)blockIdx.x * 4096 + t;  // the workgroup's 4096 blocks, 4 per thread
     uint64_t m[4];
@@ -631,9 +632,11 @@ __global__ __launch_bounds__(1024) void k_miss_list(const uint32_t* ahit, uint64
 
 __global__ __launch_bounds__(64, 4) void k_preroll(WalkArgs a, uint32_t* ahit, uint32_t* apw, uint64_t kb,
                                                    uint64_t pend, uint64_t len, const uint32_t* list,
-                                                   const unsigned long long* count, uint64_t max_miss) {
+                                                   const unsigned long long* count, uint64_t max_miss,
+                                                   const uint32_t* skip) {
     __shared__ uint32_t ntab[256];
     const uint32_t lane = threadIdx.x;
+    if (skip && skip[1]) return;  // no table is read behind a collision build that overflowed
     const uint64_t m = *count;
     // more misses than max_miss (a shifted source: every aligned window misses, and the walk
     // visits few of them): none is pre-rolled, the walk rolls the ones it meets
@@ -901,10 +904,10 @@ hipError_t launch_preroll(const WalkArgs& a, uint32_t* ahit, uint32_t* apw, uint
     {
         ProfScope ps(prof, s, "k_miss_list");
         hipLaunchKernelGGL(k_miss_list, dim3((unsigned)((b1 - b0 + 4095) / 4096)), dim3(1024), 0, s, ahit, b0, b1, list,
-                           count);
+                           count, a.skip);
     }
     ProfScope ps(prof, s, "k_preroll");
-    hipLaunchKernelGGL(k_preroll, dim3(waves), dim3(64), 0, s, a, ahit, apw, kb, pend, len, list, count, max_miss);
+    hipLaunchKernelGGL(k_preroll, dim3(waves), dim3(64), 0, s, a, ahit, apw, kb, pend, len, list, count, max_miss, a.skip);
     return hipGetLastError();
 }
 

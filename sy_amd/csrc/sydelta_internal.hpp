@@ -138,6 +138,15 @@ struct DeviceIndex {
     uint32_t* coll_state = nullptr;
     uint32_t* coll_flag = nullptr;
     uint32_t coll_cap = 0;
+    // Set (to coll_state) in the copy of the index handed to kernels queued behind a collision
+    // build whose flag nobody has read yet: they read no table when it overflowed (the fat
+    // table's fill, launch_probe's lookup, launch_preroll through WalkArgs::skip), and the
+    // host repeats them after the rebuild.
+    const uint32_t* coll_skip = nullptr;
+    // launch_index_extras: 1 the level-1 Bloom, 2 the fat table.  A scan that takes the ribbon
+    // never reads the Bloom (scan_index puts rib_l1 in its place), so the match call that
+    // queues the extras for such a scan leaves it out, and the first scan that wants it fills it.
+    uint32_t extras_parts = 3;
     FileIx* d_files = nullptr;  // per-file offsets (device copy of files)
     uint64_t* d_fblk = nullptr; // block prefix over files, nfiles+1 entries
     std::vector<FileIx> files;  // host copy
@@ -182,6 +191,8 @@ constexpr uint32_t index_coll_cap(uint64_t nblocks) {  // entries of the collisi
 }
 hipError_t launch_index_build(const uint32_t* d_weak, const uint64_t* d_strong, DeviceIndex& ix, hipStream_t s,
                               Profiler* prof, bool extras = true);
+// With ix.coll_skip set the fat table is left alone if the collision build overflowed (the
+// rebuild fills it).
 hipError_t launch_index_extras(const uint32_t* d_weak, const DeviceIndex& ix, hipStream_t s, Profiler* prof);
 // The ribbon level-1 of a built single-file index (ix.rib_l1 and its key lists set):
 // its distinct keys listed by shard from the exact table, then each shard solved.
@@ -211,7 +222,8 @@ struct DevScratch {
 // Scan all tiles of segs[0..nsegs) (device copy d_segs; block_size n <= scan_max_window()).
 // scratch (may be null: allocated and freed per call) holds the register-fed scans' pass
 // records, staged outputs and deferred list; the previous use of it must have completed
-// (the caller synchronized its stream).
+// (the caller synchronized its stream).  d_counters: 16 words, zeroed by the caller before each
+// launch ([11] is k_scan_r's run queue).
 hipError_t launch_scan(const uint8_t* d_buf, const ScanSeg* d_segs, uint32_t nsegs, uint32_t ntiles, uint32_t n,
                        const DeviceIndex& ix, const uint64_t* d_strong, uint64_t* d_hit_key, uint32_t* d_hit_val,
                        uint64_t out_cap, unsigned long long* d_counters, uint2* gfq, size_t gfq_cap, hipStream_t s,
@@ -241,6 +253,7 @@ struct ProbeJob {
 // Scratch: d_pw[nprobes], d_pst[nprobes] (the windows' weak / strong).
 // phases: 1 hash the windows (d_pw, d_pst), 2 look them up (d_out; the index must be
 // built), 3 both -- split so the hashing can run before the index is ready.
+// With ix.coll_skip set the lookup writes nothing if the collision build overflowed.
 hipError_t launch_probe(const uint8_t* d_base, const ProbeJob* d_jobs, uint32_t njobs, uint64_t nprobes,
                         uint32_t stride, uint32_t n, bool fast, const DeviceIndex& ix, uint32_t* d_pw,
                         uint64_t* d_pst, uint32_t* d_out, hipStream_t s, Profiler* prof, int phases = 3);
@@ -344,6 +357,7 @@ struct WalkArgs {
     unsigned long long* ticks;   // SYDELTA_PHASE_TIMING: 16 counters (zeroed), else null
     ExpandArgs x;                // self-indexed batches: x.ops set -> the op lists expanded on the device
     uint32_t* xdone;             // ... with per-file unit counters (zeroed)
+    const uint32_t* skip;        // launch_preroll: DeviceIndex::coll_skip
 };
 // slim: the walk of units whose aligned misses were pre-rolled (launch_preroll; a.ahit set,
 // the filter in global memory), for the units whose walk stays on the aligned grid; it marks
@@ -377,6 +391,7 @@ hipError_t launch_chunk_write(const WalkUnit* units, const WalkRec* stage, const
 // global memory; block ids below kPreMark).
 constexpr uint32_t kPreMark = 0x80000000u, kPreNone = 0xFFFFFFFEu;
 // More than max_miss misses (a shifted source): nothing is pre-rolled (the walk rolls what it meets).
+// With a.skip set (DeviceIndex::coll_skip) nothing is listed or rolled if the collision build overflowed.
 hipError_t launch_preroll(const WalkArgs& a, uint32_t* ahit, uint32_t* apw, uint64_t kb, uint64_t b0, uint64_t b1,
                           uint64_t pend, uint64_t len, uint32_t* list, unsigned long long* count, uint32_t waves,
                           uint64_t max_miss, hipStream_t s, Profiler* prof);

@@ -458,20 +458,41 @@ __global__ __launch_bounds__(64) void k_ribbon_build(const uint32_t* __restrict_
 // shard's list (q >> 22), past kRibCap in the overflow list.  Each workgroup takes `per`
 // slots: it counts its keys per shard in LDS, reserves each shard's range with one
 // global atomic, then places its keys (one global atomic per key on 1024 counters took
-// 0.25 ms at 1 Mi keys).
-constexpr uint32_t kRibListT = 256;
+// 0.25 ms at 1 Mi keys).  A thread takes kRibListK keys of each chunk of kRibListT * kRibListK
+// and loads them together (four 16-byte loads in flight where the keys are 16-byte aligned,
+// `vec`): one key per dependent iteration left the kernel waiting for memory, a load at a
+// time.  `per` is a multiple of the chunk.
+constexpr uint32_t kRibListT = 256, kRibListK = 16, kRibListChunk = kRibListT * kRibListK;
+__device__ __forceinline__ void rib_list_load(const uint32_t* __restrict__ keys, uint64_t c0, uint64_t j1, bool vec,
+                                              uint32_t (&w)[kRibListK]) {
+#pragma unroll
+    for (uint32_t g = 0; g < kRibListK / 4; ++g) {
+        const uint64_t j = c0 + ((uint64_t)g * kRibListT + threadIdx.x) * 4;
+        if (vec && j + 4 <= j1) {
+            const uint4 v = *(const uint4*)(keys + j);
+            w[g * 4] = v.x; w[g * 4 + 1] = v.y; w[g * 4 + 2] = v.z; w[g * 4 + 3] = v.w;
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < 4; ++e) w[g * 4 + e] = j + e < j1 ? keys[j + e] : kEmptyKey;
+        }
+    }
+}
 __global__ __launch_bounds__(kRibListT) void k_ribbon_list(const uint32_t* __restrict__ keys, uint64_t nslots,
-                                                           uint64_t per, uint32_t* __restrict__ rib_keys,
+                                                           uint64_t per, uint32_t vec,
+                                                           uint32_t* __restrict__ rib_keys,
                                                            uint32_t* __restrict__ rib_cnt,
                                                            uint32_t* __restrict__ rib_over) {
     __shared__ uint32_t cnt[kRibShards], base[kRibShards];
     const uint32_t tid = threadIdx.x;
     const uint64_t j0 = (uint64_t)blockIdx.x * per, j1 = min(nslots, j0 + per);
+    uint32_t w[kRibListK];
     for (uint32_t i = tid; i < kRibShards; i += kRibListT) cnt[i] = 0;
     __syncthreads();
-    for (uint64_t j = j0 + tid; j < j1; j += kRibListT) {
-        const uint32_t w = keys[j];
-        if (w != kEmptyKey) atomicAdd(&cnt[probe_hash(w).q >> 22], 1u);
+    for (uint64_t c0 = j0; c0 < j1; c0 += kRibListChunk) {
+        rib_list_load(keys, c0, j1, vec != 0, w);
+#pragma unroll
+        for (uint32_t k = 0; k < kRibListK; ++k)
+            if (w[k] != kEmptyKey) atomicAdd(&cnt[probe_hash(w[k]).q >> 22], 1u);
     }
     __syncthreads();
     for (uint32_t i = tid; i < kRibShards; i += kRibListT) {
@@ -479,14 +500,27 @@ __global__ __launch_bounds__(kRibListT) void k_ribbon_list(const uint32_t* __res
         cnt[i] = 0;
     }
     __syncthreads();
-    for (uint64_t j = j0 + tid; j < j1; j += kRibListT) {
-        const uint32_t w = keys[j];
-        if (w == kEmptyKey) continue;
-        const uint32_t sh = probe_hash(w).q >> 22;
-        const uint32_t rank = base[sh] + atomicAdd(&cnt[sh], 1u);
-        if (rank < kRibCap) rib_keys[(size_t)sh * kRibCap + rank] = w;
-        else rib_over[atomicAdd(&rib_cnt[kRibShards], 1u)] = w;  // at most nblocks distinct keys
+    for (uint64_t c0 = j0; c0 < j1; c0 += kRibListChunk) {
+        if (c0 != j0 || j1 - j0 > kRibListChunk) rib_list_load(keys, c0, j1, vec != 0, w);  // (one chunk: still held)
+        uint32_t sh[kRibListK], rank[kRibListK];
+#pragma unroll
+        for (uint32_t k = 0; k < kRibListK; ++k) {
+            sh[k] = probe_hash(w[k]).q >> 22;
+            rank[k] = w[k] != kEmptyKey ? atomicAdd(&cnt[sh[k]], 1u) : 0u;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kRibListK; ++k) {
+            if (w[k] == kEmptyKey) continue;
+            const uint32_t r = base[sh[k]] + rank[k];
+            if (r < kRibCap) rib_keys[(size_t)sh[k] * kRibCap + r] = w[k];
+            else rib_over[atomicAdd(&rib_cnt[kRibShards], 1u)] = w[k];  // at most nblocks distinct keys
+        }
     }
+}
+
+__global__ void k_ribbon_clear(uint32_t* __restrict__ rib_cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= kRibShards) rib_cnt[i] = 0;
 }
 
 // A slot's candidates from the sorted (slot, block) pairs: the run of a slot starts at start
@@ -522,14 +556,23 @@ __global__ void k_idx_cstrong(uint64_t n, const uint32_t* __restrict__ order, co
     cstrong[j] = strong[order[j]];
 }
 
+// A kernel queued behind a collision build that nobody has looked at yet is given the build's
+// state words (`skip`, DeviceIndex::coll_state; null otherwise) and reads no table when the
+// build overflowed: start / cnt may then point past order.  The host repeats it after the
+// rebuild.
+__device__ __forceinline__ bool coll_overflowed(const uint32_t* __restrict__ skip) {
+    return skip && __hip_atomic_load(&skip[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+}
+
 // Fat table of an index with a level-1 filter (k_scan_r / k_scan_g): per slot {key, first candidate in index
 // order (or kMulti | slot when the slot has more than one), that candidate's strong}, so
 // one bucket read answers a lookup (the 4 slots of a bucket are one 64-byte line).
 __global__ void k_idx_fat(uint64_t nslots, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ cnt,
                           const uint32_t* __restrict__ start, const uint32_t* __restrict__ order,
-                          const uint64_t* __restrict__ cstrong, uint4* __restrict__ fat) {
+                          const uint64_t* __restrict__ cstrong, uint4* __restrict__ fat,
+                          const uint32_t* __restrict__ skip) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nslots) return;
+    if (j >= nslots || coll_overflowed(skip)) return;
     const uint32_t k = keys[j];
     uint4 r = make_uint4(k, 0, 0, 0);
     if (k != kEmptyKey) {
@@ -636,9 +679,10 @@ __global__ __launch_bounds__(256) void k_probe_lookup(const ProbeJob* __restrict
                                                       const uint32_t* __restrict__ order,
                                                       const uint64_t* __restrict__ cstrong,
                                                       const uint32_t* __restrict__ pw, const uint64_t* __restrict__ pst,
-                                                      uint32_t* __restrict__ out) {
+                                                      uint32_t* __restrict__ out,
+                                                      const uint32_t* __restrict__ skip) {
     const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= nprobes) return;
+    if (w >= nprobes || coll_overflowed(skip)) return;
     const FileIx F = files[jobs[probe_job(jobs, njobs, w)].file];
     const uint32_t wk = pw[w];
     uint32_t best = kNoBlock;
@@ -715,7 +759,8 @@ struct ScanArgs {
     uint64_t* hit_key;   // (segment << 32) | position - segment start
     uint32_t* hit_val;   // global block index
     uint64_t out_cap;
-    unsigned long long* counters;  // [0] verified hits, [1] weak hits, [2] filter passes, [4..8) phase cycles
+    unsigned long long* counters;  // [0] verified hits, [1] weak hits, [2] filter passes, [4..8) phase cycles,
+                                   // [11] k_scan_r's run queue (runs claimed so far)
     uint2* gfq;          // k_scan_lds: per-wave filter-pass queues in HBM/L2, kGFQ entries each
     struct WDef* wdef;   // k_scan_g: weak hits whose verification k_verify_w does (count: counters[10])
     uint64_t wdef_cap;
@@ -2020,8 +2065,11 @@ __global__ __launch_bounds__(kWaves * 64, 1) void k_scan_r(ScanArgs a, uint32_t 
     uint32_t slot_file = 0xFFFFFFFFu;
     WaveOut wo = wave_out(a, gwave);
 
-    const uint32_t t_begin = blockIdx.x * per;
-    const uint32_t t_end = min(a.ntiles, t_begin + per);
+    // kSmall: the workgroup's own range of tiles, its runs claimed from an LDS counter (a wave's
+    // filter slot relies on neighbouring files); else one run queue for the whole launch,
+    // counters[11] (zeroed with the others): runs in ascending tile order, so si_hint holds
+    const uint32_t t_begin = kSmall ? blockIdx.x * per : 0u;
+    const uint32_t t_end = kSmall ? min(a.ntiles, t_begin + per) : a.ntiles;
     if (t_begin >= t_end) return;
     if (!kSmall) {
         const uint4* g = (const uint4*)a.l1;
@@ -2043,11 +2091,13 @@ __global__ __launch_bounds__(kWaves * 64, 1) void k_scan_r(ScanArgs a, uint32_t 
 #pragma unroll 1
     for (;;) {
         uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(ctr, 1u);
+        if (lane == 0) c = kSmall ? atomicAdd(ctr, 1u) : (uint32_t)atomicAdd(&a.counters[11], 1ull);
         c = __builtin_amdgcn_readfirstlane(c);
-        const uint32_t t0 = t_begin + 2 * c;
-        if (t0 >= t_end) break;
-        const uint32_t tz = min(t_end, t0 + 2);
+        // (64 bits: the launch-wide queue's c passes 2^31 where ntiles is near 2^32)
+        const uint64_t t0w = (uint64_t)t_begin + 2ull * c;
+        if (t0w >= t_end) break;
+        const uint32_t t0 = (uint32_t)t0w;
+        const uint32_t tz = (uint32_t)min((uint64_t)t_end, t0w + 2);
 #pragma unroll 1
         for (uint32_t t = t0; t < tz;) {
             // the run: host tiles t (and t+1 when in the same segment)
@@ -4684,12 +4734,19 @@ hipError_t launch_ribbon_build(const DeviceIndex& ix, hipStream_t s, Profiler* p
         nkeys = ix.nslots;
     }
     hipError_t e;
-    if ((e = hipMemsetAsync(ix.rib_cnt, 0, 4 * (kRibShards + 1), s))) return e;
-    if ((e = hipMemsetAsync(ix.rib_l1, 0, 4 * (size_t)kL1WordsR, s))) return e;
-    ProfScope ps(prof, s, "k_ribbon_build");  // listing + solving
-    const uint64_t per = std::max<uint64_t>(4096, (nkeys + 127) / 128);  // 128 workgroups
+    // the counts alone are cleared, in one launch (a memset of 4100 bytes runs as two fills).
+    // rib_l1 is not: k_ribbon_build writes every one of its kRibWords words, and the pad word
+    // behind them is read but never used -- a window's start is at most kRibBits - 32 within
+    // its shard, so the window whose second word is the pad word starts on a word boundary
+    // and alignbit's shift of 0 drops that word (k_scan_r, k_scan_g).
+    ProfScope ps(prof, s, "k_ribbon_build");  // clearing + listing + solving
+    hipLaunchKernelGGL(k_ribbon_clear, dim3(grid_for(kRibShards + 1, 256)), dim3(256), 0, s, ix.rib_cnt);
+    if ((e = hipGetLastError())) return e;
+    // 256 workgroups (one per CU) at 1 Mi keys, whole chunks each; 128 of two chunks each listed no
+    // faster, alone or beside the index build (`profiles/r08_c3_preamble_list128.txt`)
+    const uint64_t per = std::max<uint64_t>(1, ((nkeys + 255) / 256 + kRibListChunk - 1) / kRibListChunk) * kRibListChunk;
     hipLaunchKernelGGL(k_ribbon_list, dim3((uint32_t)((nkeys + per - 1) / per)), dim3(kRibListT), 0, s, keys, nkeys,
-                       per, ix.rib_keys, ix.rib_cnt, ix.rib_over);
+                       per, (uint32_t)(((uintptr_t)keys & 15) == 0), ix.rib_keys, ix.rib_cnt, ix.rib_over);
     if ((e = hipGetLastError())) return e;
     hipLaunchKernelGGL(k_ribbon_build, dim3(kRibShards), dim3(64), 0, s, ix.rib_keys, ix.rib_cnt, ix.rib_over,
                        ix.rib_l1);
@@ -4708,13 +4765,15 @@ hipError_t launch_index_extras(const uint32_t* d_weak, const DeviceIndex& ix, hi
     hipError_t e;
     if (!ix.l1 || !ix.nblocks) return hipSuccess;
     ProfScope ps(prof, s, "k_idx_extras");
-    if ((e = hipMemsetAsync(ix.l1, 0, l1_total_words(ix.l1_wshift) * 4, s))) return e;
-    hipLaunchKernelGGL(k_idx_l1, dim3(grid_for(ix.nblocks, 256)), dim3(256), 0, s, d_weak, ix.nblocks, ix.l1,
-                       ix.l1_wshift);
-    if ((e = hipGetLastError())) return e;
-    if (ix.fat)
+    if (ix.extras_parts & 1) {
+        if ((e = hipMemsetAsync(ix.l1, 0, l1_total_words(ix.l1_wshift) * 4, s))) return e;
+        hipLaunchKernelGGL(k_idx_l1, dim3(grid_for(ix.nblocks, 256)), dim3(256), 0, s, d_weak, ix.nblocks, ix.l1,
+                           ix.l1_wshift);
+        if ((e = hipGetLastError())) return e;
+    }
+    if (ix.fat && (ix.extras_parts & 2))
         hipLaunchKernelGGL(k_idx_fat, dim3(grid_for(ix.nslots, 256)), dim3(256), 0, s, (uint64_t)ix.nslots, ix.keys,
-                           ix.cnt, ix.start, ix.order, ix.cstrong, ix.fat);
+                           ix.cnt, ix.start, ix.order, ix.cstrong, ix.fat, ix.coll_skip);
     return hipGetLastError();
 }
 
@@ -4783,7 +4842,7 @@ hipError_t launch_index_build(const uint32_t* d_weak, const uint64_t* d_strong, 
     if ((e = hipGetLastError())) return e;
     if (extras && ix.fat)
         hipLaunchKernelGGL(k_idx_fat, dim3(grid_for(ix.nslots, 256)), dim3(256), 0, s, (uint64_t)ix.nslots, ix.keys,
-                           ix.cnt, ix.start, ix.order, ix.cstrong, ix.fat);
+                           ix.cnt, ix.start, ix.order, ix.cstrong, ix.fat, (const uint32_t*)nullptr);
     return hipGetLastError();
 }
 
@@ -4809,7 +4868,7 @@ hipError_t launch_probe(const uint8_t* d_base, const ProbeJob* d_jobs, uint32_t 
     if (!(phases & 2)) return hipSuccess;
     ProfScope ps(prof, s, "k_probe_lookup");
     hipLaunchKernelGGL(k_probe_lookup, dim3(grid_for(nprobes, 256)), dim3(256), 0, s, d_jobs, njobs, nprobes,
-                       ix.d_files, ix.filt, ix.keys, ix.start, ix.cnt, ix.order, ix.cstrong, d_pw, d_pst, d_out);
+                       ix.d_files, ix.filt, ix.keys, ix.start, ix.cnt, ix.order, ix.cstrong, d_pw, d_pst, d_out, ix.coll_skip);
     return hipGetLastError();
 }
 
@@ -4971,7 +5030,9 @@ hipError_t launch_scan(const uint8_t* d_buf, const ScanSeg* d_segs, uint32_t nse
         const int waves = 12;
         const uint32_t small_words = small_r ? std::max<uint32_t>(ix.max_fwords, 64u) : 0u;
         constexpr LdsR LR = ldsr_layout();
-        // one workgroup per CU over contiguous host tiles, an even number each (runs are pairs)
+        // one workgroup per CU.  Small indexes: each over contiguous host tiles, an even number
+        // (runs are pairs); else `per` only sizes the grid and the waves claim runs from
+        // d_counters[11], which the caller has zeroed with the others
         uint32_t per = (uint32_t)((ntiles + (uint64_t)r_cus - 1) / (uint64_t)r_cus);
         per += per & 1;
         const uint32_t grid = (uint32_t)((ntiles + (uint64_t)per - 1) / per);
