@@ -43,7 +43,8 @@ extern "C" int sydelta_xxh3_batch_device(int device, const uint8_t* d_buf, uint6
     std::iota(order.begin(), order.end(), 0u);
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return nb[a] > nb[b]; });
     const uint64_t tab = nfiles * 8 * 3 + (nfiles + 1) * 8 + nact * 8 + (nact + 1) * 8 + nfiles * 4;
-    const uint64_t bytes = (tab + 255) / 256 * 256 + xxh_chain_records(npieces) * 64;
+    const uint64_t nb_max = *std::max_element(nb.begin(), nb.end());
+    const uint64_t bytes = (tab + 255) / 256 * 256 + xxh_scratch_records(npieces, nb_max) * 8;
     DevBuf ws;
     HIP_TRY(ws.alloc(bytes, s));
     uint64_t* d_off = ws.at<uint64_t>();

@@ -465,8 +465,35 @@ hipError_t launch_hash_blocks(const uint8_t* d_buf, uint64_t len, uint64_t bs, c
 // Whole-file XXH3-64 of files (d_off[f], d_len[f]) of d_buf: d_pfx = prefix of full
 // 1 KiB block counts ((len-1)/1024 for len > 240, else 0), (d_aoff, d_apfx) the same
 // for the nact files with >= 1 block (d_apfx[nact] = npieces), d_order = files by block
-// count descending, d_C = 8 rows of xxh_chain_records(npieces) u64 of scratch, d_out[f] = hash.
-constexpr uint64_t xxh_chain_records(uint64_t npieces) { return npieces + 3 * 32; }
+// count descending, d_C = xxh_scratch_records(npieces, nb_max) u64 of scratch (nb_max = the
+// largest block count of a file), d_out[f] = hash.
+//
+// The scratch is 8 rows (one per accumulator) of xxh_chain_records(npieces) u64, then a
+// tail.  A lane of k_xxh_chain prefetches its row in batches of kChainBatch without a bound
+// check, from its own file's first record up to the longest chain of its wave: with chains
+// of nmin..nmax steps in the wave it loads up to record fpfx[f] + 1 + xxh_chain_last_load(nmin,
+// nmax) of its row, <= fpfx[f] + nmax + 3 * kChainBatch - 1.  For the file that owns nmax
+// (nb = nmax + 1 blocks) that stays inside the row's 3 * kChainBatch records of slack; a
+// shorter file of the same wave, which may lie anywhere in the row, passes the row's end by
+// up to nmax < nb_max records (fpfx[f] <= npieces).  Rows 0-6 run over into the next row,
+// row 7 into the tail of nb_max records.  What is loaded past a chain's own steps is never
+// used.  tests/csrc/xxh_scratch_check.cpp checks the bound on the host tables of batches.
+constexpr int kChainBatch = 32;
+constexpr uint64_t xxh_chain_records(uint64_t npieces) { return npieces + 3 * kChainBatch; }
+constexpr uint64_t xxh_scratch_records(uint64_t npieces, uint64_t nb_max) {
+    return 8 * xxh_chain_records(npieces) + nb_max;
+}
+// Last index of Cn (= the lane's first record + 1) that k_xxh_chain loads in a wave whose
+// chains have nmin..nmax steps: the prologue loads Cn[0, kChainBatch); a round of the
+// every-chain loop (k + 2 * kChainBatch <= nmin) loads up to Cn[k + 3 * kChainBatch - 1], which
+// is Cn[k' + kChainBatch - 1] for the k' it leaves; a round of the ragged loop (k < nmax)
+// loads up to Cn[k + 3 * kChainBatch - 1].
+constexpr uint64_t xxh_chain_last_load(uint64_t nmin, uint64_t nmax) {
+    const uint64_t round = 2 * kChainBatch;
+    const uint64_t k = nmin / round * round;  // where the every-chain loop stops
+    if (nmax <= k) return k + kChainBatch - 1;
+    return (nmax - 1) / round * round + 3 * kChainBatch - 1;
+}
 hipError_t launch_xxh_files(const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len, const uint64_t* d_pfx,
                             const uint64_t* d_aoff, const uint64_t* d_apfx, uint64_t nact, const uint32_t* d_order,
                             uint64_t nfiles, uint64_t npieces, uint64_t* d_C, uint64_t* d_out,

@@ -4529,8 +4529,10 @@ __device__ __forceinline__ Y2 chain_step(Y2 y, uint64_t c, uint32_t klo, uint32_
     return r;
 }
 
-constexpr int kChainBatch = 32;
-static_assert(xxh_chain_records(0) == 3 * kChainBatch, "C row slack must cover the batch prefetch");
+// kChainBatch, the row slack and the scratch tail: sydelta_internal.hpp (xxh_chain_last_load).
+static_assert(xxh_chain_records(0) == 3 * kChainBatch && xxh_chain_last_load(0, 1) + 1 == xxh_chain_records(0) &&
+                  xxh_chain_last_load(2 * kChainBatch, 2 * kChainBatch) == 3 * kChainBatch - 1,
+              "C row slack must cover the batch prefetch of the wave's longest chain");
 
 // Phase B: lanes 8g..8g+7 of a wave hash file order[8 * blockIdx.x + g]; lane i keeps
 // acc[i].  Files are ordered by size so the eight chains of a wave have similar lengths.
@@ -4559,8 +4561,11 @@ __global__ __launch_bounds__(64) void k_xxh_chain(const uint8_t* __restrict__ bu
     const uint64_t y0 = c_tab.init[i] + Ci[0];  // another file's record (or slack) when nb == 0: unused
     Y2 y{(uint32_t)y0, (uint32_t)(y0 >> 32)};
     const uint64_t* Cn = Ci + 1;          // the addend of step k is C_{k+1}
-    // Two register batches: the chain consumes one while the other is in flight.  C rows
-    // have 3 * kChainBatch entries of slack, so batch loads never need a bound check.
+    // Two register batches: the chain consumes one while the other is in flight.  The
+    // loads run to the wave's longest chain without a bound check: the row's 3 * kChainBatch
+    // records of slack cover the file that owns nmax, a shorter file of the wave reads up
+    // to nmax records past its row, into the next row or, from row 7, the scratch's tail
+    // (xxh_scratch_records).  Those values are never used (k + j < steps).
     uint64_t ba[kChainBatch], bb[kChainBatch];
 #pragma unroll
     for (int j = 0; j < kChainBatch; ++j) ba[j] = Cn[j];

@@ -1,6 +1,7 @@
 """BLAKE3-256 on the device (k_b3_chunks + k_b3_tree) against the from-specification
 reference of tests/blake3_ref.py: block and chunk edges, tail blocks, one wave of chunks and
-the launches above it, unaligned file starts, ragged batches, pieces of a sharded file
+the launches above it, unaligned file starts, ragged batches, batches whose files share
+waves (every chunk count from 1 to 66; level-1 nodes packed one launch up), pieces of a sharded file
 joined on the host, a caller's stream, and the streamed path API."""
 import random
 
@@ -87,6 +88,46 @@ def test_batch_of_single_chunk_files(gpu):
     got = gpu.blake3_batch(buf, offs, lens)
     for f, (o, ln) in enumerate(zip(offs, lens)):
         assert got[f].tobytes() == R.blake3(blob[o:o + ln]), (f, o, ln)
+
+
+def _check_shared_waves(gpu, chunk_counts, seed):
+    """A batch of files of the given chunk counts, file n of (n - 1) KiB + 1 B (n odd) or n KiB
+    (n even) and always the same bytes, at unaligned starts with gaps of 0-18 bytes."""
+    import torch
+
+    rng = random.Random(seed)
+    lens = [(n - 1) * KIB + (1 if n & 1 else KIB) for n in chunk_counts]
+    offs, pos = [], 0
+    for ln in lens:
+        pos += rng.randrange(0, 19)
+        offs.append(pos)
+        pos += ln
+    buf = torch.zeros(pos + 64, dtype=torch.uint8, device="cuda")
+    for o, ln in zip(offs, lens):
+        buf[o:o + ln] = torch.frombuffer(bytearray(_data(ln)), dtype=torch.uint8).cuda()
+    got = gpu.blake3_batch(buf, offs, lens)
+    bad = [(f, n) for f, n in enumerate(chunk_counts) if got[f].tobytes() != _expect(lens[f])]
+    assert not bad, bad[:10]
+
+
+@pytest.mark.parametrize("order", ["shuffled", "ascending", "descending"])
+def test_batch_of_every_chunk_count_in_shared_waves(order, gpu):
+    """Files of 3 to 64 chunks sit at power-of-two slots (seg_align) of waves they share with
+    their neighbours, and wave_levels finds a node's sibling at lane ^ 2^l: every chunk count
+    from 1 to 66, with different alignments side by side."""
+    counts = list(range(1, 67))
+    if order == "shuffled":
+        random.Random(66).shuffle(counts)
+    elif order == "descending":
+        counts.reverse()
+    _check_shared_waves(gpu, counts, seed=len(order))
+
+
+def test_batch_packs_level_one_nodes(gpu):
+    """The same packing one launch up: files of 65 to 4096 chunks leave 2 to 64 nodes that share
+    a k_b3_tree wave (here 2, 2, 3, 4 and 33), between files that finished in the first launch;
+    the file of 4097 chunks (65 nodes) alone needs a third launch."""
+    _check_shared_waves(gpu, [65, 1, 128, 3, 129, 64, 193, 1, 2112, 3, 4097, 64, 3], seed=5)
 
 
 def test_batch_rejects_out_of_range(gpu):
